@@ -18,7 +18,12 @@ Contract (driver):
 launched for N>1 as one rank per GPU via torch.distributed.run; rank 0
 prints ONE JSON line; value = WHOLE-JOB req/s over all ranks (weak scaling:
 each rank runs its own gateway + sessions + backend shard; discovery state
-is broadcast over RCCL/gloo first).
+is broadcast over RCCL/gloo first).  Such a plain run sets up, warms up,
+times the K steps and prints the line, nothing else.  --dump-outputs DIR
+also writes one step's response bodies as .npy arrays (same arguments ->
+same inputs -> comparable outputs across builds); --full is where any
+secondary measurement belongs (none exist today: every other workload is a
+--config run of its own).
 
 Configs (BASELINE.json):
   --config hello1k   SERVING: hello SayHello, 1 KB bodies, --batch sessions
@@ -90,6 +95,16 @@ def parse_args():
                     help="override config.gpu.streams (engine instances)")
     ap.add_argument("--reactors", type=int, default=0,
                     help="override config.server.reactors (serving config)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the response bodies of "
+                         "one step as DIR/<name>.npy (float32/float64, "
+                         "<= 64 MB; see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements and checks.  "
+                         "A plain run does only what the headline figure "
+                         "needs; this benchmark has no secondary work of its "
+                         "own (other workloads are separate --config runs), "
+                         "so today --full runs exactly the plain run")
     return ap.parse_args()
 
 
@@ -150,6 +165,88 @@ def make_bodies(cfg_name: str, batch: int, payload_bytes: int, seed: int,
         for i in range(batch):
             bodies.append(jsonrpc_body(tool, wide_payload(rng, target_bytes=size), i + 1))
     return bodies
+
+
+def http_step_responses(host: str, port: int, body: bytes, sessions: int,
+                        timeout_s: float = 30.0):
+    """One serving step seen from the client side: `sessions` keep-alive
+    connections each POST `body` once (all in flight together, the way the
+    load generator's sessions are) and the response BODIES come back in
+    session order."""
+    import socket
+
+    socks = []
+    try:
+        for s in range(sessions):
+            sk = socket.create_connection((host, port), timeout=timeout_s)
+            sk.setsockopt(socket.IPPROTO_TCP, socket.TCP_NODELAY, 1)
+            socks.append(sk)
+        for s, sk in enumerate(socks):
+            sk.sendall(
+                b"POST / HTTP/1.1\r\nHost: b\r\n"
+                b"Content-Type: application/json\r\n"
+                b"Mcp-Session-Id: dump-%d\r\nContent-Length: %d\r\n\r\n"
+                % (s, len(body)) + body)
+        out = []
+        for sk in socks:
+            buf = b""
+            while True:
+                he = buf.find(b"\r\n\r\n")
+                if he >= 0:
+                    head = buf[:he].lower()
+                    p = head.find(b"content-length:")
+                    if p < 0:
+                        raise RuntimeError(f"no Content-Length: {buf[:200]!r}")
+                    cl = int(head[p + 15:].split(b"\r\n", 1)[0])
+                    if len(buf) >= he + 4 + cl:
+                        out.append(buf[he + 4:he + 4 + cl])
+                        break
+                chunk = sk.recv(1 << 16)
+                if not chunk:
+                    raise RuntimeError("gateway closed a dump connection")
+                buf += chunk
+        return out
+    finally:
+        for sk in socks:
+            sk.close()
+
+
+# float32 elements written to responses.npy at most (48 MB, so the whole
+# dump stays under 64 MB with the two small index arrays)
+DUMP_MAX_ELEMS = 12 * 1024 * 1024
+
+
+def dump_outputs(out_dir: str, responses) -> None:
+    """Write one step's response bodies (what a caller of the timed path
+    receives) as .npy arrays:
+
+      responses.npy         float32 [rows, width]: the bytes of each sampled
+                            response, padded with -1 to the longest one
+      response_rows.npy     float64 [rows]: which responses were sampled
+                            (all of them when they fit; otherwise a fixed,
+                            seeded sample in ascending order)
+      response_lengths.npy  float64 [n]: byte length of EVERY response
+
+    A step whose responses exceed the size budget keeps whole rows; only
+    when a single response is larger than the budget is it cut to a prefix.
+    """
+    import numpy as np
+
+    n = len(responses)
+    lengths = np.array([len(r) for r in responses], dtype=np.float64)
+    width = min(int(lengths.max()) if n else 0, DUMP_MAX_ELEMS)
+    rows = min(n, max(1, DUMP_MAX_ELEMS // max(1, width)))
+    picked = (list(range(n)) if rows >= n
+              else sorted(random.Random(20240607).sample(range(n), rows)))
+    arr = np.full((len(picked), width), -1.0, dtype=np.float32)
+    for k, i in enumerate(picked):
+        r = np.frombuffer(bytes(responses[i])[:width], dtype=np.uint8)
+        arr[k, :r.size] = r
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "responses.npy"), arr)
+    np.save(os.path.join(out_dir, "response_rows.npy"),
+            np.array(picked, dtype=np.float64))
+    np.save(os.path.join(out_dir, "response_lengths.npy"), lengths)
 
 
 def main() -> None:
@@ -432,7 +529,7 @@ def main() -> None:
             t0 = time.perf_counter()
             for _ in range(args.steps):
                 s0 = time.perf_counter()
-                step()
+                out = step()
                 step_times.append(time.perf_counter() - s0)
             if use_gpu:
                 torch.cuda.synchronize()
@@ -446,6 +543,16 @@ def main() -> None:
                              device="cuda" if use_gpu and dist.get_backend() == "nccl" else "cpu")
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
+
+        if args.dump_outputs and rank == 0:
+            if serving:
+                # the load generator counts and discards response bytes, and
+                # every session posts the same body at every step, so each
+                # step's responses are this body's responses: take them from
+                # one more, untimed, step through the same gateway
+                out = http_step_responses("127.0.0.1", http_port, bodies[0],
+                                          args.batch)
+            dump_outputs(args.dump_outputs, out)
 
         total_requests = args.batch * args.steps * world
         reqs_per_s = total_requests / elapsed

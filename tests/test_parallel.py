@@ -8,6 +8,7 @@ shard affinity.
 
 import json
 import os
+from pathlib import Path
 
 import pytest
 import torch.multiprocessing as mp
@@ -120,10 +121,43 @@ def test_world2_gloo(tmp_path):
             assert json.load(f)["ok"]
 
 
+@pytest.fixture
+def sock_dir(tmp_path):
+    """Directory short enough for an AF_UNIX socket path.
+
+    sun_path holds at most 107 bytes, and pytest's tmp_path can be longer
+    than that under a deeply nested TMPDIR; then a short-named directory
+    under a system temp root is used (and removed afterwards) instead."""
+    import shutil
+    import tempfile
+
+    def fits(d):
+        return len(os.fsencode(os.path.join(str(d), "hello.sock"))) <= 100
+
+    if fits(tmp_path):
+        yield tmp_path
+        return
+    made = None
+    for root in (tempfile.gettempdir(), "/tmp", "/dev/shm"):
+        try:
+            made = tempfile.mkdtemp(prefix="ggs", dir=root)
+        except OSError:
+            continue
+        if fits(made):
+            break
+        shutil.rmtree(made, ignore_errors=True)
+        made = None
+    assert made, "no writable temp dir short enough for a unix socket path"
+    try:
+        yield Path(made)
+    finally:
+        shutil.rmtree(made, ignore_errors=True)
+
+
 @pytest.mark.timeout(180)
 @pytest.mark.parametrize("use_descriptor", [True, False],
                          ids=["descriptor", "reflection"])
-def test_serve_dp_world2_shared_port(tmp_path, use_descriptor):
+def test_serve_dp_world2_shared_port(tmp_path, sock_dir, use_descriptor):
     """tools/serve_dp.py end to end: two gateway ranks (gloo, CPU pipeline)
     share ONE port via SO_REUSEPORT, rank 0 discovers (descriptor file OR
     live reflection) and broadcasts the snapshot, and real HTTP tool calls
@@ -138,7 +172,7 @@ def test_serve_dp_world2_shared_port(tmp_path, use_descriptor):
     from examples.protos import ALL_FDPS
     from google.protobuf import descriptor_pb2
 
-    sock_path = str(tmp_path / "hello.sock")
+    sock_path = str(sock_dir / "hello.sock")
     server, _ = serve_hello(target=f"unix:{sock_path}")
     try:
         fdset = descriptor_pb2.FileDescriptorSet()

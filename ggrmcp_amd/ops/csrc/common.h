@@ -102,7 +102,9 @@ enum : uint8_t {
 };
 
 // protobuf wire types
-enum : uint32_t { W_VARINT = 0, W_I64 = 1, W_LEN = 2, W_I32 = 5 };
+enum : uint32_t {
+  W_VARINT = 0, W_I64 = 1, W_LEN = 2, W_SGROUP = 3, W_EGROUP = 4, W_I32 = 5
+};
 
 // ---------------------------------------------------------------------------
 // Per-request records (kernel <-> host)
@@ -147,6 +149,11 @@ struct __attribute__((packed)) DecodeResult {
   uint32_t pad;
 };
 static_assert(sizeof(DecodeResult) == 16, "DecodeResult layout");
+
+// protojson value ranges of the time WKTs (both directions refuse the rest)
+constexpr int64_t TS_MIN_SECONDS = -62135596800ll;  // 0001-01-01T00:00:00Z
+constexpr int64_t TS_MAX_SECONDS = 253402300799ll;  // 9999-12-31T23:59:59Z
+constexpr int64_t DUR_MAX_SECONDS = 315576000000ll; // +-10000 years
 
 // JSON-RPC id storage per slot (raw JSON token bytes, e.g. `17` or `"abc"`)
 constexpr int ID_SLOT_BYTES = 48;

@@ -541,7 +541,17 @@ DEV int b64_val(uint8_t ch) {
 // decode src[0..n) into out (lane0 stores); returns length or 0xFFFFFFFF
 DEV uint32_t b64_decode(Ctx& c, const uint8_t* src, uint32_t n, uint8_t* dst,
                         uint32_t cap) {
-  while (n && src[n - 1] == '=') --n;
+  // at most two trailing pads, and an unpadded length of 1 mod 4 cannot
+  // encode whole bytes; '=' anywhere else fails the alphabet check below
+  uint32_t pads = 0;
+  while (n && src[n - 1] == '=') {
+    --n;
+    ++pads;
+  }
+  if (pads > 2 || (n & 3u) == 1u) return 0xFFFFFFFF;
+  // padded input is padded to a whole quantum (Go's strict decoder; "AA="
+  // is neither the padded nor the raw form of anything)
+  if (pads && ((n + pads) & 3u)) return 0xFFFFFFFF;
   uint32_t o = 0, acc = 0, nbits = 0;
   for (uint32_t i = 0; i < n; ++i) {
     int v = b64_val(src[i]);
@@ -692,8 +702,8 @@ DEV bool parse_timestamp(Ctx& c, const uint8_t* s, uint32_t n, int64_t* secs,
   auto dig = [&](uint32_t i) -> int { return s[i] - '0'; };
   for (uint32_t i : {0u, 1u, 2u, 3u, 5u, 6u, 8u, 9u, 11u, 12u, 14u, 15u, 17u, 18u})
     if (s[i] < '0' || s[i] > '9') return false;
-  if (s[4] != '-' || s[7] != '-' || (s[10] != 'T' && s[10] != 't') || s[13] != ':' ||
-      s[16] != ':')
+  // RFC 3339 as protojson reads it: upper-case 'T' and 'Z' only
+  if (s[4] != '-' || s[7] != '-' || s[10] != 'T' || s[13] != ':' || s[16] != ':')
     return false;
   int64_t y = dig(0) * 1000 + dig(1) * 100 + dig(2) * 10 + dig(3);
   int64_t mo = dig(5) * 10 + dig(6);
@@ -701,24 +711,37 @@ DEV bool parse_timestamp(Ctx& c, const uint8_t* s, uint32_t n, int64_t* secs,
   int64_t hh = dig(11) * 10 + dig(12);
   int64_t mi = dig(14) * 10 + dig(15);
   int64_t ss = dig(17) * 10 + dig(18);
+  // calendar validity: a real day of a real month (Feb 29 on leap years only)
+  bool leap = (y % 4 == 0 && y % 100 != 0) || y % 400 == 0;
+  int64_t dim = mo == 2 ? (leap ? 29 : 28)
+                        : (mo == 4 || mo == 6 || mo == 9 || mo == 11) ? 30 : 31;
+  if (y < 1 || mo < 1 || mo > 12 || da < 1 || da > dim || hh > 23 || mi > 59 ||
+      ss > 59)
+    return false;
   uint32_t i = 19;
   int32_t ns = 0;
   if (i < n && s[i] == '.') {
     ++i;
     int scale = 100000000;
+    uint32_t nd = 0;
     while (i < n && s[i] >= '0' && s[i] <= '9') {
       ns += (s[i] - '0') * scale;
       scale /= 10;
       ++i;
+      ++nd;
     }
+    if (nd < 1 || nd > 9) return false;  // nanosecond precision at most
   }
   int64_t tz = 0;
-  if (i < n && (s[i] == 'Z' || s[i] == 'z')) {
+  if (i < n && s[i] == 'Z') {
     ++i;
   } else if (i < n && (s[i] == '+' || s[i] == '-')) {
     if (i + 6 > n || s[i + 3] != ':') return false;
+    for (uint32_t k : {1u, 2u, 4u, 5u})
+      if (s[i + k] < '0' || s[i + k] > '9') return false;
     int64_t th = (s[i + 1] - '0') * 10 + (s[i + 2] - '0');
     int64_t tm = (s[i + 4] - '0') * 10 + (s[i + 5] - '0');
+    if (th > 23 || tm > 59) return false;  // RFC 3339 time-numoffset
     tz = (th * 3600 + tm * 60) * (s[i] == '+' ? 1 : -1);
     i += 6;
   } else {
@@ -727,7 +750,8 @@ DEV bool parse_timestamp(Ctx& c, const uint8_t* s, uint32_t n, int64_t* secs,
   if (i != n) return false;
   *secs = days_from_civil(y, mo, da) * 86400 + hh * 3600 + mi * 60 + ss - tz;
   *nanos = ns;
-  return true;
+  // 0001-01-01T00:00:00Z .. 9999-12-31T23:59:59Z after the offset is applied
+  return *secs >= TS_MIN_SECONDS && *secs <= TS_MAX_SECONDS;
 }
 
 DEV bool parse_duration(const uint8_t* s, uint32_t n, int64_t* secs, int32_t* nanos) {
@@ -741,8 +765,11 @@ DEV bool parse_duration(const uint8_t* s, uint32_t n, int64_t* secs, int32_t* na
   }
   int64_t sec = 0;
   bool any = false;
+  // at least one digit before the point, and one after it if there is one
+  if (i >= n || s[i] < '0' || s[i] > '9') return false;
   while (i < n && s[i] >= '0' && s[i] <= '9') {
     sec = sec * 10 + (s[i] - '0');
+    if (sec > DUR_MAX_SECONDS) return false;  // +-10000 years (also no overflow)
     ++i;
     any = true;
   }
@@ -750,12 +777,15 @@ DEV bool parse_duration(const uint8_t* s, uint32_t n, int64_t* secs, int32_t* na
   if (i < n && s[i] == '.') {
     ++i;
     int scale = 100000000;
+    uint32_t nd = 0;
     while (i < n && s[i] >= '0' && s[i] <= '9') {
       ns += (s[i] - '0') * scale;
       scale /= 10;
       ++i;
+      ++nd;
       any = true;
     }
+    if (nd < 1 || nd > 9) return false;  // 1..9 digits: nanosecond precision
   }
   if (!any || i != n) return false;
   *secs = neg ? -sec : sec;
@@ -842,7 +872,7 @@ DEVN bool encode_scalar_field(Ctx& c, const FieldEntry& f) {
         return emit_fixed64(c, bits);
       }
       float fv = (float)d;
-      if (isinf(fv) && !isinf(d) && !nonf)  // out of float range
+      if (isinf(fv) && !nonf)  // finite text out of float (or double) range
         return fail(c, E_INVALID_PARAMS, (int)f.number);
       if (!emit_tag(c, f.number, W_I32)) return false;
       return emit_fixed32(c, __builtin_bit_cast(uint32_t, fv));
@@ -993,8 +1023,16 @@ DEV bool encode_packed_element(Ctx& c, const FieldEntry& f) {
       else if (nonf == 2) d = nan("");
       else d = nv.cls == 0 ? (nv.neg ? -(double)nv.mag : (double)nv.mag) : nv.d;
       if (nv.imprecise && !nonf) return fail(c, E_UNSUPPORTED, (int)f.number);
-      if (f.kind == K_DOUBLE) return emit_fixed64(c, __builtin_bit_cast(uint64_t, d));
-      return emit_fixed32(c, __builtin_bit_cast(uint32_t, (float)d));
+      // finite text out of the field's range: protojson rejects (same rule
+      // as the singular path in encode_scalar_field)
+      if (f.kind == K_DOUBLE) {
+        if (isinf(d) && !nonf) return fail(c, E_INVALID_PARAMS, (int)f.number);
+        return emit_fixed64(c, __builtin_bit_cast(uint64_t, d));
+      }
+      float fv = (float)d;
+      if (isinf(fv) && !nonf)
+        return fail(c, E_INVALID_PARAMS, (int)f.number);
+      return emit_fixed32(c, __builtin_bit_cast(uint32_t, fv));
     }
     case K_ENUM: {
       skip_ws(c);
@@ -1015,7 +1053,8 @@ DEV bool encode_packed_element(Ctx& c, const FieldEntry& f) {
       }
       if (!parse_numeric_value(c, &nv, false, &nonf)) return false;
       int64_t v;
-      if (!num_to_i64(nv, &v)) return fail(c, E_INVALID_PARAMS, (int)f.number);
+      if (!num_to_i64(nv, &v) || v < -2147483648ll || v > 2147483647ll)
+        return fail(c, E_INVALID_PARAMS, (int)f.number);
       return emit_varint(c, (uint64_t)v);
     }
     default: {
@@ -1174,7 +1213,7 @@ DEVN int encode_value_scalar_or_classify(Ctx& c, uint32_t* slot) {
 
 // FieldMask field: JSON "a.b,camelCase" -> repeated snake_case strings
 // (message payload only; caller owns tag/len)
-DEVN bool encode_fieldmask_payload(Ctx& c) {
+DEVN bool encode_fieldmask_payload(Ctx& c, uint32_t fnum) {
   uint32_t st, rl;
   bool esc;
   if (!string_span(c, &st, &rl, &esc)) return false;
@@ -1189,6 +1228,11 @@ DEVN bool encode_fieldmask_payload(Ctx& c) {
       if (!reserve_len(c, &slot)) return false;
       for (uint32_t k = i; k < j; ++k) {
         uint8_t ch = c.s[st + k];
+        // a JSON path is camelCase; '_' cannot map back from snake_case
+        if (ch == '_') return fail(c, E_INVALID_PARAMS, (int)fnum);
+        // no empty name segment ("a..b", ".a", "a.")
+        if (ch == '.' && (k == i || k + 1 == j || c.s[st + k + 1] == '.'))
+          return fail(c, E_INVALID_PARAMS, (int)fnum);
         if (ch >= 'A' && ch <= 'Z') {
           if (c.opos + 2 > c.ocap) return fail(c, E_OVERFLOW);
           if (!c.lane) {
@@ -1203,9 +1247,12 @@ DEVN bool encode_fieldmask_payload(Ctx& c) {
         }
       }
       if (!backfill_len(c, slot)) return false;
+    } else {
+      return fail(c, E_INVALID_PARAMS, (int)fnum);  // empty path ("a,,b")
     }
     i = j + 1;
   }
+  if (rl && c.s[st + rl - 1] == ',') return fail(c, E_INVALID_PARAMS, (int)fnum);
   return true;
 }
 
@@ -1249,8 +1296,8 @@ DEVN bool encode_map_entry_key(Ctx& c, const FieldEntry& f, const FieldEntry& kf
     }
     case K_BOOL: {
       uint64_t v;
-      if (krl == 4 && c.s[kst] == 't') v = 1;
-      else if (krl == 5 && c.s[kst] == 'f') v = 0;
+      if (krl == 4 && wave_equal(c, c.s + kst, (const uint8_t*)"true", 4)) v = 1;
+      else if (krl == 5 && wave_equal(c, c.s + kst, (const uint8_t*)"false", 5)) v = 0;
       else return fail(c, E_INVALID_PARAMS, (int)f.number);
       if (!emit_tag(c, 1, W_VARINT)) return false;
       return emit_varint(c, v);
@@ -1269,9 +1316,14 @@ DEVN bool encode_map_entry_key(Ctx& c, const FieldEntry& f, const FieldEntry& kf
         case K_SINT32:
         case K_SFIXED32:
           if (!num_to_i64(nv, &sv)) return fail(c, E_INVALID_PARAMS, (int)f.number);
+          if ((kf.kind == K_INT32 || kf.kind == K_SINT32 || kf.kind == K_SFIXED32) &&
+              (sv < -2147483648ll || sv > 2147483647ll))
+            return fail(c, E_INVALID_PARAMS, (int)f.number);
           break;
         default:
           if (!num_to_u64(nv, &uv)) return fail(c, E_INVALID_PARAMS, (int)f.number);
+          if ((kf.kind == K_UINT32 || kf.kind == K_FIXED32) && uv > 0xFFFFFFFFull)
+            return fail(c, E_INVALID_PARAMS, (int)f.number);
           sv = (int64_t)uv;
       }
       if (kf.kind == K_SINT64) uv = zigzag64(sv);
@@ -1321,7 +1373,7 @@ DEVN int encode_msgfield_value(Ctx& c, const FieldEntry& f, uint8_t* push_mode,
       if (!emit_tag(c, f.number, W_LEN)) return 0;
       uint32_t slot;
       if (!reserve_len(c, &slot)) return 0;
-      if (!encode_fieldmask_payload(c)) return 0;
+      if (!encode_fieldmask_payload(c, f.number)) return 0;
       return backfill_len(c, slot) ? 1 : 0;
     }
     case WKT_EMPTY: {
@@ -1542,7 +1594,7 @@ DEV bool encode_walk(Ctx& c, int top_msg_idx, int wg_item = 0,
       }
       EPUSH(EM_LIST, -1, slots0, 0);
     } else if (m.wkt_kind == WKT_FIELDMASK) {
-      return encode_fieldmask_payload(c);
+      return encode_fieldmask_payload(c, 0);
     } else if (m.wkt_kind == WKT_EMPTY) {
       if (!expect(c, '{')) return false;
       skip_ws(c);

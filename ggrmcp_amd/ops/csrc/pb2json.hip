@@ -392,7 +392,12 @@ DEVN bool emit_double_body(DCtx& c, double d, bool as_float) {
     return true;
   }
   // shortest precision whose parse-back round-trips
-  int p_lo = as_float ? 6 : 15;
+  // (starting at 6/15 digits is sound for NORMAL values only: their rounding
+  // interval is too narrow to hold a shorter decimal that the 6/15-digit
+  // rounding would not reproduce with trailing zeros.  float32 subnormals
+  // carry fewer mantissa bits — 8.9561e-41 printed as 8.95612e-41 — so
+  // their search starts at one digit; double subnormals go to the host.)
+  int p_lo = as_float ? (d < 1.1754943508222875e-38 ? 1 : 6) : 15;
   int p_hi = as_float ? 9 : 17;
   int e10 = 0;
   uint64_t digits = 0;
@@ -532,6 +537,11 @@ DEV uint32_t put_nanos(uint8_t* o, int32_t nanos) {
 }
 
 DEVN bool put_timestamp(DCtx& c, int64_t secs, int32_t nanos) {
+  // protojson refuses to print years outside 0001-9999 or nanos outside
+  // [0, 1e9): hand the slot to the host so the real error text surfaces
+  if (secs < TS_MIN_SECONDS || secs > TS_MAX_SECONDS || nanos < 0 ||
+      nanos > 999999999)
+    return dfail(c, E_UNSUPPORTED);
   if (c.opos + 40 > c.ocap) return dfail(c, E_OVERFLOW);
   uint8_t buf[40];
   uint32_t n = 0;
@@ -566,6 +576,11 @@ DEVN bool put_timestamp(DCtx& c, int64_t secs, int32_t nanos) {
 }
 
 DEVN bool put_duration(DCtx& c, int64_t secs, int32_t nanos) {
+  // protojson refuses +-10000 years, |nanos| >= 1e9 and seconds/nanos of
+  // opposite sign (same host hand-off as put_timestamp)
+  if (secs < -DUR_MAX_SECONDS || secs > DUR_MAX_SECONDS || nanos < -999999999 ||
+      nanos > 999999999 || (secs > 0 && nanos < 0) || (secs < 0 && nanos > 0))
+    return dfail(c, E_UNSUPPORTED);
   if (c.opos + 40 > c.ocap) return dfail(c, E_OVERFLOW);
   uint8_t buf[40];
   uint32_t n = 0;
@@ -593,6 +608,13 @@ DEV bool read_varint(DCtx& c, uint64_t* v) {
   return true;
 }
 
+// a field tag: field number 0 is malformed wire (every parser refuses it)
+DEV bool read_tag(DCtx& c, uint64_t* tag) {
+  if (!get_varint(c.pb, c.len, &c.pos, tag) || (*tag >> 3) == 0)
+    return dfail(c, E_PARSE);
+  return true;
+}
+
 DEV bool read_fixed32(DCtx& c, uint32_t* v) {
   if (c.pos + 4 > c.len) return dfail(c, E_PARSE);
   *v = (uint32_t)c.pb[c.pos] | ((uint32_t)c.pb[c.pos + 1] << 8) |
@@ -610,9 +632,13 @@ DEV bool read_fixed64(DCtx& c, uint64_t* v) {
   return true;
 }
 
-DEV bool skip_wire(DCtx& c, uint32_t wt) {
+DEVN bool skip_group(DCtx& c, uint32_t number);
+
+// skip one field's payload; `number` is its field number (groups need it)
+DEV bool skip_wire(DCtx& c, uint32_t wt, uint32_t number) {
   uint64_t v;
   switch (wt) {
+    case W_SGROUP: return skip_group(c, number);
     case W_VARINT: return read_varint(c, &v);
     case W_I64:
       if (c.pos + 8 > c.len) return dfail(c, E_PARSE);
@@ -620,7 +646,7 @@ DEV bool skip_wire(DCtx& c, uint32_t wt) {
       return true;
     case W_LEN: {
       if (!read_varint(c, &v)) return false;
-      if (c.pos + v > c.len) return dfail(c, E_PARSE);
+      if (v > c.len - c.pos) return dfail(c, E_PARSE);
       c.pos += (uint32_t)v;
       return true;
     }
@@ -630,6 +656,50 @@ DEV bool skip_wire(DCtx& c, uint32_t wt) {
       return true;
   }
   return dfail(c, E_PARSE);
+}
+
+// unknown group (start tag of field `number` consumed): skip to its end
+// tag.  Iterative; an end tag must carry the number of the group it closes
+// (cold path, so a small addressable stack is fine).  c.pos only ever moves
+// forward: every length is compared against the bytes that remain.
+constexpr uint32_t MAX_GROUP_NEST = 8;
+DEVN bool skip_group(DCtx& c, uint32_t number) {
+  uint32_t open[MAX_GROUP_NEST];
+  uint32_t depth = 1;
+  open[0] = number;
+  while (depth) {
+    uint64_t tag, v;
+    if (!read_tag(c, &tag)) return false;
+    switch ((uint32_t)(tag & 7)) {
+      case W_SGROUP:
+        // deeper nesting than the stack holds: the host transcodes
+        if (depth == MAX_GROUP_NEST) return dfail(c, E_UNSUPPORTED);
+        open[depth++] = (uint32_t)(tag >> 3);
+        break;
+      case W_EGROUP:
+        if ((uint32_t)(tag >> 3) != open[depth - 1]) return dfail(c, E_PARSE);
+        --depth;
+        break;
+      case W_VARINT:
+        if (!read_varint(c, &v)) return false;
+        break;
+      case W_I64:
+        if (c.pos + 8 > c.len) return dfail(c, E_PARSE);
+        c.pos += 8;
+        break;
+      case W_LEN:
+        if (!read_varint(c, &v)) return false;
+        if (v > c.len - c.pos) return dfail(c, E_PARSE);
+        c.pos += (uint32_t)v;
+        break;
+      case W_I32:
+        if (c.pos + 4 > c.len) return dfail(c, E_PARSE);
+        c.pos += 4;
+        break;
+      default: return dfail(c, E_PARSE);
+    }
+  }
+  return true;
 }
 
 DEV const FieldEntry* find_field(DCtx& c, const MsgEntry& m, uint32_t number) {
@@ -757,14 +827,14 @@ DEVN bool emit_scalar_value(DCtx& c, const FieldEntry& f) {
     }
     case K_STRING: {
       if (!read_varint(c, &v)) return false;
-      if (c.pos + v > c.len) return dfail(c, E_PARSE);
+      if (v > c.len - c.pos) return dfail(c, E_PARSE);
       if (!put_json_string(c, c.pb + c.pos, (uint32_t)v)) return false;
       c.pos += (uint32_t)v;
       return true;
     }
     case K_BYTES: {
       if (!read_varint(c, &v)) return false;
-      if (c.pos + v > c.len) return dfail(c, E_PARSE);
+      if (v > c.len - c.pos) return dfail(c, E_PARSE);
       if (!putc_(c, '"')) return false;
       if (!put_base64(c, c.pb + c.pos, (uint32_t)v)) return false;
       c.pos += (uint32_t)v;
@@ -798,7 +868,7 @@ DEVN bool emit_map_key(DCtx& c, const FieldEntry& kf, uint32_t key_pos,
     switch (kf.kind) {
       case K_STRING: {
         ok = read_varint(c, &v);
-        if (ok && c.pos + v > c.len) ok = dfail(c, E_PARSE);
+        if (ok && v > c.len - c.pos) ok = dfail(c, E_PARSE);
         if (ok) ok = put_escaped(c, c.pb + c.pos, (uint32_t)v);
         break;
       }
@@ -849,7 +919,12 @@ DEVN bool emit_map_key(DCtx& c, const FieldEntry& kf, uint32_t key_pos,
     c.pos = save;
     if (!ok) return false;
   } else {
-    if (kf.kind != K_STRING && !putc_(c, '0')) return false;
+    // absent key = the key type's default
+    if (kf.kind == K_BOOL) {
+      if (!puts_(c, "false", 5)) return false;
+    } else if (kf.kind != K_STRING && !putc_(c, '0')) {
+      return false;
+    }
   }
   if (!putc_(c, '"')) return false;
   return putc_(c, ':');
@@ -886,7 +961,7 @@ DEVN bool decode_ts_dur_body(DCtx& c, uint32_t end, bool is_ts) {
   int32_t nanos = 0;
   while (c.pos < end) {
     uint64_t tag;
-    if (!read_varint(c, &tag)) return false;
+    if (!read_tag(c, &tag)) return false;
     uint32_t num = (uint32_t)(tag >> 3);
     if (num == 1 && (tag & 7) == W_VARINT) {
       uint64_t v;
@@ -897,7 +972,7 @@ DEVN bool decode_ts_dur_body(DCtx& c, uint32_t end, bool is_ts) {
       if (!read_varint(c, &v)) return false;
       nanos = (int32_t)(int64_t)v;
     } else {
-      if (!skip_wire(c, (uint32_t)(tag & 7))) return false;
+      if (!skip_wire(c, (uint32_t)(tag & 7), (uint32_t)(tag >> 3))) return false;
     }
   }
   return is_ts ? put_timestamp(c, secs, nanos) : put_duration(c, secs, nanos);
@@ -908,12 +983,12 @@ DEVN bool decode_wrapper_body(DCtx& c, const MsgEntry& m, uint32_t end) {
   bool emitted = false;
   while (c.pos < end) {
     uint64_t tag;
-    if (!read_varint(c, &tag)) return false;
+    if (!read_tag(c, &tag)) return false;
     if ((uint32_t)(tag >> 3) == 1) {
       if (!emit_scalar_value(c, inner)) return false;
       emitted = true;
     } else {
-      if (!skip_wire(c, (uint32_t)(tag & 7))) return false;
+      if (!skip_wire(c, (uint32_t)(tag & 7), (uint32_t)(tag >> 3))) return false;
     }
   }
   if (!emitted) {
@@ -933,19 +1008,23 @@ DEVN bool decode_fieldmask_body(DCtx& c, uint32_t end) {
   bool first = true;
   while (c.pos < end) {
     uint64_t tag;
-    if (!read_varint(c, &tag)) return false;
+    if (!read_tag(c, &tag)) return false;
     if ((uint32_t)(tag >> 3) != 1 || (tag & 7) != W_LEN) {
-      if (!skip_wire(c, (uint32_t)(tag & 7))) return false;
+      if (!skip_wire(c, (uint32_t)(tag & 7), (uint32_t)(tag >> 3))) return false;
       continue;
     }
     uint64_t slen;
     if (!read_varint(c, &slen)) return false;
-    if (c.pos + slen > c.len) return dfail(c, E_PARSE);
+    if (slen > c.len - c.pos) return dfail(c, E_PARSE);
     if (!first && !putc_(c, ',')) return false;
     first = false;
     bool up = false;  // snake -> camel
     for (uint32_t i = 0; i < (uint32_t)slen; ++i) {
       uint8_t ch = c.pb[c.pos + i];
+      // the camelCase form must convert back to the same path: no upper
+      // case, and every '_' is followed by a lower-case letter
+      if (ch >= 'A' && ch <= 'Z') return dfail(c, E_UNSUPPORTED);
+      if (up && !(ch >= 'a' && ch <= 'z')) return dfail(c, E_UNSUPPORTED);
       if (ch == '_') {
         up = true;
         continue;
@@ -954,6 +1033,7 @@ DEVN bool decode_fieldmask_body(DCtx& c, uint32_t end) {
       up = false;
       if (!putc_(c, ch)) return false;
     }
+    if (up) return dfail(c, E_UNSUPPORTED);  // trailing '_'
     c.pos += (uint32_t)slen;
   }
   return putc_(c, '"');
@@ -1004,7 +1084,7 @@ DEVN int enter_body(DCtx& c, int msg_idx, uint32_t vend, uint8_t* push_mode,
       // one-shot oneof; nested struct/list push frames
       if (c.pos >= vend) return puts_(c, "null", 4) ? 1 : 0;
       uint64_t tag;
-      if (!read_varint(c, &tag)) return 0;
+      if (!read_tag(c, &tag)) return 0;
       uint32_t num = (uint32_t)(tag >> 3);
       uint64_t v;
       switch (num) {
@@ -1013,10 +1093,15 @@ DEVN int enter_body(DCtx& c, int msg_idx, uint32_t vend, uint8_t* push_mode,
           return puts_(c, "null", 4) ? 1 : 0;
         case 2:
           if (!read_fixed64(c, &v)) return 0;
+          {
+            // JSON has no NaN/Infinity: protojson refuses Value.number_value
+            double d = __builtin_bit_cast(double, v);
+            if (d != d || isinf(d)) return dfail(c, E_UNSUPPORTED) ? 1 : 0;
+          }
           return put_double(c, __builtin_bit_cast(double, v), false) ? 1 : 0;
         case 3: {
           if (!read_varint(c, &v)) return 0;
-          if (c.pos + v > c.len) return dfail(c, E_PARSE) ? 1 : 0;
+          if (v > c.len - c.pos) return dfail(c, E_PARSE) ? 1 : 0;
           if (!put_json_string(c, c.pb + c.pos, (uint32_t)v)) return 0;
           c.pos += (uint32_t)v;
           return 1;
@@ -1027,7 +1112,7 @@ DEVN int enter_body(DCtx& c, int msg_idx, uint32_t vend, uint8_t* push_mode,
         case 5:
         case 6: {
           if (!read_varint(c, &v)) return 0;
-          if (c.pos + v > c.len) return dfail(c, E_PARSE) ? 1 : 0;
+          if (v > c.len - c.pos) return dfail(c, E_PARSE) ? 1 : 0;
           const FieldEntry* sf = find_field(c, m, num);
           if (!sf) return dfail(c, E_UNSUPPORTED) ? 1 : 0;
           // unwrap the nested Struct/ListValue HERE: re-entering through a
@@ -1069,18 +1154,18 @@ DEVN bool map_entry_step(DCtx& c, DFrame& f, uint32_t eend, DFrame* stack,
     uint32_t save0 = c.pos;
     bool committed = false;
     uint64_t tag;
-    if (!read_varint(c, &tag)) return false;
+    if (!read_tag(c, &tag)) return false;
     if ((tag >> 3) == 1 && (uint32_t)(tag & 7) == expected_wire(kf)) {
       uint32_t kp = c.pos;
-      if (!skip_wire(c, (uint32_t)(tag & 7))) return false;
+      if (!skip_wire(c, (uint32_t)(tag & 7), (uint32_t)(tag >> 3))) return false;
       if (c.pos < eend) {
         uint64_t vtag;
-        if (!read_varint(c, &vtag)) return false;
+        if (!read_tag(c, &vtag)) return false;
         if ((vtag >> 3) == 2) {
           if (vf.kind == K_MESSAGE) {
             uint64_t v;
             if (!read_varint(c, &v)) return false;
-            if (c.pos + v > c.len) return dfail(c, E_PARSE);
+            if (v > c.len - c.pos) return dfail(c, E_PARSE);
             uint32_t vend = c.pos + (uint32_t)v;
             if (vend == eend) {
               // commit: emit key, then enter/push the message value
@@ -1121,8 +1206,8 @@ DEVN bool map_entry_step(DCtx& c, DFrame& f, uint32_t eend, DFrame* stack,
             if (!emit_scalar_value(c, vf)) return false;
             while (c.pos < eend) {
               uint64_t t2;
-              if (!read_varint(c, &t2)) return false;
-              if (!skip_wire(c, (uint32_t)(t2 & 7))) return false;
+              if (!read_tag(c, &t2)) return false;
+              if (!skip_wire(c, (uint32_t)(t2 & 7), (uint32_t)(t2 >> 3))) return false;
             }
             committed = true;
           }
@@ -1136,7 +1221,7 @@ DEVN bool map_entry_step(DCtx& c, DFrame& f, uint32_t eend, DFrame* stack,
   uint32_t key_pos = 0, val_pos = 0;
   while (c.pos < eend) {
     uint64_t tag;
-    if (!read_varint(c, &tag)) return false;
+    if (!read_tag(c, &tag)) return false;
     uint32_t num = (uint32_t)(tag >> 3);
     if (num == 1) {
       have_key = true;
@@ -1145,7 +1230,7 @@ DEVN bool map_entry_step(DCtx& c, DFrame& f, uint32_t eend, DFrame* stack,
       have_val = true;
       val_pos = c.pos;
     }
-    if (!skip_wire(c, (uint32_t)(tag & 7))) return false;
+    if (!skip_wire(c, (uint32_t)(tag & 7), (uint32_t)(tag >> 3))) return false;
   }
   if (!emit_map_key(c, kf, key_pos, have_key)) return false;
   if (!have_val) {
@@ -1157,7 +1242,7 @@ DEVN bool map_entry_step(DCtx& c, DFrame& f, uint32_t eend, DFrame* stack,
   if (vf.kind == K_MESSAGE) {
     uint64_t v;
     if (!read_varint(c, &v)) return false;
-    if (c.pos + v > c.len) return dfail(c, E_PARSE);
+    if (v > c.len - c.pos) return dfail(c, E_PARSE);
     uint32_t vend = c.pos + (uint32_t)v;
     uint8_t pm = FM_BODY;
     int32_t pidx = vf.sub_index;
@@ -1245,7 +1330,7 @@ DEV bool decode_walk(DCtx& c, int top_msg_idx, uint32_t top_end,
       if (c.pos < f.end) {
         uint32_t save = c.pos;
         uint64_t ntag;
-        if (!read_varint(c, &ntag)) return false;
+        if (!read_tag(c, &ntag)) return false;
         if ((uint32_t)(ntag >> 3) == f.cont_num) {
           more = true;
           wt = (uint32_t)(ntag & 7);
@@ -1259,23 +1344,27 @@ DEV bool decode_walk(DCtx& c, int top_msg_idx, uint32_t top_end,
         continue;
       }
       const FieldEntry& fe = c.t.fields[f.cont_field];
-      if (!putc_(c, ',')) return false;
+      // mid-array wire-type mismatch (an unknown field to the parsers): the
+      // array is already open, so the host transcodes the slot
+      if (wt != expected_wire(fe) && wt != W_LEN) return dfail(c, E_UNSUPPORTED);
       if (wt == W_LEN && expected_wire(fe) != W_LEN) {
         uint64_t plen;
         if (!read_varint(c, &plen)) return false;
         uint32_t pend = c.pos + (uint32_t)plen;
-        if (pend > c.len) return dfail(c, E_PARSE);
-        bool first = false;  // comma already emitted? emit_packed prepends
-        // emit_packed writes separators before each elem when !first; we
-        // already wrote one comma, so mark first=true for the first elem
-        first = true;
+        if (plen > c.len - c.pos) return dfail(c, E_PARSE);
+        if (plen == 0) continue;  // empty packed run: no element, no comma
+        if (!putc_(c, ',')) return false;
+        // emit_packed writes separators before each elem when !first; the
+        // comma is already out, so the first elem goes bare
+        bool first = true;
         if (!emit_packed(c, fe, pend, &first)) return false;
         continue;
       }
+      if (!putc_(c, ',')) return false;
       if (fe.kind == K_MESSAGE) {
         uint64_t v;
         if (!read_varint(c, &v)) return false;
-        if (c.pos + v > c.len) return dfail(c, E_PARSE);
+        if (v > c.len - c.pos) return dfail(c, E_PARSE);
         uint32_t vend = c.pos + (uint32_t)v;
         uint8_t pm = FM_BODY;
         int32_t pidx = fe.sub_index;
@@ -1316,7 +1405,7 @@ DEV bool decode_walk(DCtx& c, int top_msg_idx, uint32_t top_end,
       if (c.pos < f.end) {
         uint32_t save = c.pos;
         uint64_t ntag;
-        if (!read_varint(c, &ntag)) return false;
+        if (!read_tag(c, &ntag)) return false;
         if ((uint32_t)(ntag >> 3) == f.cont_num) {
           more = true;
         } else {
@@ -1335,7 +1424,7 @@ DEV bool decode_walk(DCtx& c, int top_msg_idx, uint32_t top_end,
       uint64_t elen;
       if (!read_varint(c, &elen)) return false;
       uint32_t eend = c.pos + (uint32_t)elen;
-      if (eend > c.len) return dfail(c, E_PARSE);
+      if (elen > c.len - c.pos) return dfail(c, E_PARSE);
       int pushed = 0;
       if (!map_entry_step(c, f, eend, stack, sp, &pushed)) return false;
       continue;
@@ -1349,15 +1438,15 @@ DEV bool decode_walk(DCtx& c, int top_msg_idx, uint32_t top_end,
         continue;
       }
       uint64_t tag;
-      if (!read_varint(c, &tag)) return false;
+      if (!read_tag(c, &tag)) return false;
       if ((uint32_t)(tag >> 3) != 1 || (tag & 7) != W_LEN) {
-        if (!skip_wire(c, (uint32_t)(tag & 7))) return false;
+        if (!skip_wire(c, (uint32_t)(tag & 7), (uint32_t)(tag >> 3))) return false;
         continue;
       }
       uint64_t elen;
       if (!read_varint(c, &elen)) return false;
       uint32_t eend = c.pos + (uint32_t)elen;
-      if (eend > c.len) return dfail(c, E_PARSE);
+      if (elen > c.len - c.pos) return dfail(c, E_PARSE);
       if (!f.first_member && !putc_(c, ',')) return false;
       f.first_member = 0;
       const MsgEntry& m = c.t.msgs[f.msg_idx];
@@ -1394,15 +1483,15 @@ DEV bool decode_walk(DCtx& c, int top_msg_idx, uint32_t top_end,
         continue;
       }
       uint64_t tag;
-      if (!read_varint(c, &tag)) return false;
+      if (!read_tag(c, &tag)) return false;
       if ((uint32_t)(tag >> 3) != 1 || (tag & 7) != W_LEN) {
-        if (!skip_wire(c, (uint32_t)(tag & 7))) return false;
+        if (!skip_wire(c, (uint32_t)(tag & 7), (uint32_t)(tag >> 3))) return false;
         continue;
       }
       uint64_t elen;
       if (!read_varint(c, &elen)) return false;
       uint32_t eend = c.pos + (uint32_t)elen;
-      if (eend > c.len) return dfail(c, E_PARSE);
+      if (elen > c.len - c.pos) return dfail(c, E_PARSE);
       if (!f.first_member && !putc_(c, ',')) return false;
       f.first_member = 0;
       const MsgEntry& m = c.t.msgs[f.msg_idx];
@@ -1421,13 +1510,28 @@ DEV bool decode_walk(DCtx& c, int top_msg_idx, uint32_t top_end,
       continue;
     }
     uint64_t tag;
-    if (!read_varint(c, &tag)) return false;
+    if (!read_tag(c, &tag)) return false;
     uint32_t num = (uint32_t)(tag >> 3), wt = (uint32_t)(tag & 7);
     const MsgEntry& m = c.t.msgs[f.msg_idx];
     const FieldEntry* fe = find_field(c, m, num);
     if (fe == nullptr) {
-      if (!skip_wire(c, wt)) return false;  // unknown field: dropped
+      if (!skip_wire(c, wt, num)) return false;  // unknown field: dropped
       continue;
+    }
+    // a known field carried in another wire type is an UNKNOWN field to
+    // every protobuf parser (packable repeated fields take both encodings)
+    if (wt != expected_wire(*fe) && !((fe->flags & F_REPEATED) && wt == W_LEN)) {
+      if (!skip_wire(c, wt, num)) return false;
+      continue;
+    }
+    // an empty packed run carries no element: nothing to print, and it
+    // neither opens the array nor counts as an occurrence of the field
+    if ((fe->flags & F_REPEATED) && wt == W_LEN && expected_wire(*fe) != W_LEN) {
+      uint32_t save = c.pos;
+      uint64_t plen;
+      if (!read_varint(c, &plen)) return false;
+      if (plen == 0) continue;
+      c.pos = save;
     }
     // out-of-order / non-adjacent duplicates -> host transcodes
     if (num <= f.prev_number) return dfail(c, E_UNSUPPORTED);
@@ -1475,7 +1579,7 @@ DEV bool decode_walk(DCtx& c, int top_msg_idx, uint32_t top_end,
       uint64_t elen;
       if (!read_varint(c, &elen)) return false;
       uint32_t eend = c.pos + (uint32_t)elen;
-      if (eend > c.len) return dfail(c, E_PARSE);
+      if (elen > c.len - c.pos) return dfail(c, E_PARSE);
       f.cont_field = (int32_t)(fe - c.t.fields);
       f.cont_num = num;
       f.cont_kind = CK_MAP;
@@ -1493,7 +1597,7 @@ DEV bool decode_walk(DCtx& c, int top_msg_idx, uint32_t top_end,
         uint64_t plen;
         if (!read_varint(c, &plen)) return false;
         uint32_t pend = c.pos + (uint32_t)plen;
-        if (pend > c.len) return dfail(c, E_PARSE);
+        if (plen > c.len - c.pos) return dfail(c, E_PARSE);
         bool first = true;
         if (!emit_packed(c, *fe, pend, &first)) return false;
         continue;
@@ -1501,7 +1605,7 @@ DEV bool decode_walk(DCtx& c, int top_msg_idx, uint32_t top_end,
       if (fe->kind == K_MESSAGE) {
         uint64_t v;
         if (!read_varint(c, &v)) return false;
-        if (c.pos + v > c.len) return dfail(c, E_PARSE);
+        if (v > c.len - c.pos) return dfail(c, E_PARSE);
         uint32_t vend = c.pos + (uint32_t)v;
         uint8_t pm = FM_BODY;
         int32_t pidx = fe->sub_index;
@@ -1536,7 +1640,7 @@ DEV bool decode_walk(DCtx& c, int top_msg_idx, uint32_t top_end,
       if (wt != W_LEN) return dfail(c, E_PARSE);
       uint64_t v;
       if (!read_varint(c, &v)) return false;
-      if (c.pos + v > c.len) return dfail(c, E_PARSE);
+      if (v > c.len - c.pos) return dfail(c, E_PARSE);
       uint32_t vend = c.pos + (uint32_t)v;
       uint8_t pm = FM_BODY;
       int32_t pidx = fe->sub_index;
@@ -1895,7 +1999,7 @@ extern "C" __global__ void __launch_bounds__(WG_DEC_WAVES * WAVE) k_pb2json_wg(
       } else if (wt == W_LEN) {
         uint64_t v;
         if (!get_varint(pb, wire_len, &pos, &v)) { ok = false; break; }
-        if (pos + v > wire_len) { ok = false; break; }
+        if (v > wire_len - pos) { ok = false; break; }
         pos += (uint32_t)v;
       } else {
         ok = false;

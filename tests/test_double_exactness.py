@@ -109,3 +109,25 @@ def test_parse_correctly_rounded(env):
         assert msg.weight == expect, (t, msg.weight, expect)
     # fallbacks are the long-mantissa generator classes, not the common case
     assert fallbacks < len(texts) // 2
+
+
+# ---- float32 twins -----------------------------------------------------------
+# ``float`` fields take their own path (digits_roundtrip_f on decode, the
+# (float) narrowing on encode); the generators and oracles are shared with
+# the device twin through tests/protojson_corpus.py.
+
+@pytest.fixture(scope="module")
+def fenv():
+    import protojson_corpus as pc
+
+    return pc, pc.make_env(HostSimEngine)
+
+
+def test_float32_format_shortest_roundtrip(fenv):
+    pc, e = fenv
+    assert pc.check_float32_format(e, seed=2025) is None
+
+
+def test_float32_parse_correctly_rounded(fenv):
+    pc, e = fenv
+    assert pc.check_float32_parse(e, seed=4049) is None

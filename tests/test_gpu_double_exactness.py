@@ -106,3 +106,23 @@ def test_gpu_parse_correctly_rounded(env):
             continue
         msg = cpu.pb_to_message(desc, w)
         assert msg.weight == expect, (t, msg.weight, expect)
+
+
+# ---- float32 twins (generators/oracles in tests/protojson_corpus.py) ---------
+
+@pytest.fixture(scope="module")
+def fenv():
+    import protojson_corpus as pc
+    from ggrmcp_amd.engine.batch import GpuEngine
+
+    return pc, pc.make_env(lambda infos: GpuEngine(infos, device=0))
+
+
+def test_gpu_float32_format_shortest_roundtrip(fenv):
+    pc, e = fenv
+    assert pc.check_float32_format(e, seed=31338) is None
+
+
+def test_gpu_float32_parse_correctly_rounded(fenv):
+    pc, e = fenv
+    assert pc.check_float32_parse(e, seed=778) is None

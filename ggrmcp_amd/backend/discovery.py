@@ -223,7 +223,11 @@ class ServiceDiscoverer:
     def encode_request(self, mi: MethodInfo, input_json: str) -> bytes:
         """JSON -> protobuf wire bytes (reference reflection.go:351-357)."""
         in_cls, _ = self._message_classes(mi)
-        msg = json_format.Parse(input_json or "{}", in_cls())
+        # the descriptor's own pool resolves google.protobuf.Any type URLs
+        msg = json_format.Parse(
+            input_json or "{}", in_cls(),
+            descriptor_pool=mi.input_descriptor.file.pool,
+        )
         return msg.SerializeToString()
 
     def decode_response(self, mi: MethodInfo, wire: bytes) -> str:
@@ -231,7 +235,8 @@ class ServiceDiscoverer:
         _, out_cls = self._message_classes(mi)
         msg = out_cls.FromString(wire)
         return json_format.MessageToJson(
-            msg, indent=None, ensure_ascii=False, preserving_proto_field_name=False
+            msg, indent=None, ensure_ascii=False, preserving_proto_field_name=False,
+            descriptor_pool=mi.output_descriptor.file.pool,
         )
 
     def invoke_wire(

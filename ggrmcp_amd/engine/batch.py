@@ -174,6 +174,7 @@ class GpuEngine:
             tool_paths=tool_paths,
             tool_out_msg=tool_out_msg,
             tool_backend=tool_backend,
+            type_table=self.tables.type_table,
         )
         self.stats = stats if stats is not None else EngineStats()
         # re-entrant: a span holds the engine for its whole encode ->

@@ -3,9 +3,14 @@
 Uses google.protobuf.json_format (the canonical protojson implementation,
 same semantics as the reference's protojson.Unmarshal/Marshal at
 reflection.go:351-381).  Also serves as the explicit per-request fallback
-for batch slots the kernels flag E_UNSUPPORTED (google.protobuf.Any,
-out-of-order wire fields, oversized ids) — counted in engine stats, never
-silent.
+for batch slots the kernels flag E_UNSUPPORTED (out-of-order wire fields,
+oversized ids, the google.protobuf.Any shapes listed under "Host-escape
+rules" in docs/KERNELS.md) — counted in engine stats, never silent.
+
+Both directions pass the message's OWN descriptor pool: the gateway's
+descriptors live in a private pool (descriptors/loader.py), and the type
+URL of a google.protobuf.Any must resolve there, not in protobuf's
+default pool.
 """
 
 from __future__ import annotations
@@ -28,13 +33,16 @@ class CpuTranscoder:
         return cls
 
     def json_to_pb(self, desc: Descriptor, json_text: str) -> bytes:
-        msg = json_format.Parse(json_text or "{}", self._cls(desc)())
+        msg = json_format.Parse(
+            json_text or "{}", self._cls(desc)(), descriptor_pool=desc.file.pool
+        )
         return msg.SerializeToString()
 
     def pb_to_json(self, desc: Descriptor, wire: bytes) -> str:
         msg = self._cls(desc).FromString(wire)
         return json_format.MessageToJson(
-            msg, indent=None, ensure_ascii=False, preserving_proto_field_name=False
+            msg, indent=None, ensure_ascii=False, preserving_proto_field_name=False,
+            descriptor_pool=desc.file.pool,
         )
 
     def pb_to_message(self, desc: Descriptor, wire: bytes):

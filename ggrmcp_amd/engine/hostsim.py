@@ -37,6 +37,7 @@ class HostSimEngine:
         self._eng = mod.HostEngine(
             t.msg_table, t.field_table, t.enum_table, t.enum_values,
             t.tool_table, t.name_blob, t.n_msgs, t.n_tools,
+            type_table=t.type_table,
         )
 
     def encode_batch(

@@ -15,7 +15,12 @@ tables; the HIP kernels walk these instead of doing any reflection:
   directions;
 * ``tool_table``  — tool-name hash -> input/output message indices (the GPU
   resolves ``params.name`` itself during envelope parsing);
-* ``name_blob``   — UTF-8 bytes of every name referenced above.
+* ``name_blob``   — UTF-8 bytes of every name referenced above;
+* ``type_table``  — message full-name hash -> message index, sorted by hash
+  (``google.protobuf.Any`` payload resolution).  Built only when some tool
+  reaches an Any; then every message of every descriptor file reachable
+  from the tools' files is compiled too, because a type that is only ever
+  packed into an Any is referenced by no field.
 
 Layouts are mirrored by static_asserts in ops/csrc/common.h; keep in sync.
 Tables are deterministic functions of the (sorted) tool map, so every DP
@@ -47,10 +52,13 @@ ENUM_VALUE_FMT = "<QiIHHi"  # hash, number, name_off, name_len, pad, pad2 -> 24 
 ENUM_VALUE_SIZE = struct.calcsize(ENUM_VALUE_FMT)
 TOOL_ENTRY_FMT = "<QiiIHH"  # hash, in_msg, out_msg, name_off, name_len, flags
 TOOL_ENTRY_SIZE = struct.calcsize(TOOL_ENTRY_FMT)
+TYPE_ENTRY_FMT = "<QiIHHi"  # hash, msg_idx, name_off, name_len, pad, pad2 -> 24 B
+TYPE_ENTRY_SIZE = struct.calcsize(TYPE_ENTRY_FMT)
 
 assert FIELD_ENTRY_SIZE == 40, FIELD_ENTRY_SIZE
 assert ENUM_VALUE_SIZE == 24
 assert TOOL_ENTRY_SIZE == 24
+assert TYPE_ENTRY_SIZE == 24
 
 # field flags
 F_REPEATED = 1
@@ -118,6 +126,7 @@ class CompiledTables:
     msg_index: Dict[str, int]  # message full name -> index
     tool_index: Dict[str, int]  # tool name -> index
     tool_order: List[str]  # index -> tool name
+    type_table: bytes = b""  # empty unless a tool reaches google.protobuf.Any
 
     def blobs(self) -> Tuple[bytes, ...]:
         return (
@@ -127,6 +136,7 @@ class CompiledTables:
             self.enum_values,
             self.tool_table,
             self.name_blob,
+            self.type_table,
         )
 
     def checksum(self) -> int:
@@ -178,6 +188,33 @@ class TableCompiler:
         self.enums.append(desc)
         return idx
 
+    def _add_any_universe(self, tools: Dict[str, MethodInfo]) -> None:
+        """Add every message an Any may carry: all non-map-entry messages
+        (nested ones included) of every file reachable from the tools' files,
+        in sorted-full-name order so every rank compiles identical bytes."""
+        files = {}
+        todo = []
+        for name in sorted(tools):
+            mi = tools[name]
+            todo += [mi.input_descriptor.file, mi.output_descriptor.file]
+        while todo:
+            fd = todo.pop()
+            if fd.name in files:
+                continue
+            files[fd.name] = fd
+            todo.extend(fd.dependencies)
+        found: Dict[str, Descriptor] = {}
+        for fd in files.values():
+            pending = list(fd.message_types_by_name.values())
+            while pending:
+                d = pending.pop()
+                if d.GetOptions().map_entry:
+                    continue
+                found[d.full_name] = d
+                pending.extend(d.nested_types)
+        for full_name in sorted(found):
+            self._add_message(found[full_name])
+
     def compile(self, tools: Dict[str, MethodInfo]) -> CompiledTables:
         # deterministic ordering: sorted tool names drive everything
         tool_names = sorted(tools)
@@ -188,6 +225,9 @@ class TableCompiler:
             out_idx = self._add_message(mi.output_descriptor)
             flags = T_SERVER_STREAMING if mi.is_server_streaming else 0
             tool_rows.append((name, in_idx, out_idx, flags))
+        has_any = "google.protobuf.Any" in self.msg_index
+        if has_any:
+            self._add_any_universe(tools)
 
         # message + field tables (self.msgs grows during iteration as nested
         # types are discovered, so iterate by index)
@@ -288,7 +328,26 @@ class TableCompiler:
                 )
             )
 
+        # type table (Any payload resolution); absent without an Any so the
+        # other blobs stay byte-identical for Any-free tool maps
+        type_rows = []
+        if has_any:
+            for idx, desc in enumerate(self.msgs):
+                if desc.GetOptions().map_entry:
+                    continue
+                name_off, name_len = self._intern(desc.full_name)
+                type_rows.append(
+                    (fnv1a64(desc.full_name.encode()), idx, name_off, name_len)
+                )
+            type_rows.sort()
+        type_entries = bytearray()
+        for h, idx, name_off, name_len in type_rows:
+            type_entries.extend(
+                struct.pack(TYPE_ENTRY_FMT, h, idx, name_off, name_len, 0, 0)
+            )
+
         return CompiledTables(
+            type_table=bytes(type_entries),
             msg_table=bytes(msg_entries),
             field_table=bytes(field_entries),
             enum_table=bytes(enum_entries),

@@ -70,6 +70,18 @@ struct __attribute__((packed)) ToolEntry {
 };
 static_assert(sizeof(ToolEntry) == 24, "ToolEntry layout");
 
+// message full-name hash -> message index, sorted by hash: resolves the type
+// URL of a google.protobuf.Any.  Empty unless some tool reaches an Any.
+struct __attribute__((packed)) TypeEntry {
+  uint64_t hash;      // FNV-1a64 of the message full name
+  int32_t msg_idx;
+  uint32_t name_off;  // full name in name_blob
+  uint16_t name_len;
+  uint16_t pad;
+  int32_t pad2;
+};
+static_assert(sizeof(TypeEntry) == 24, "TypeEntry layout");
+
 // field flags (tables.py F_*)
 enum : uint8_t {
   F_REPEATED = 1,
@@ -176,7 +188,12 @@ struct Tables {
   const uint8_t* names;
   int32_t n_msgs;
   int32_t n_tools;
+  const TypeEntry* types;
+  int32_t n_types;
 };
+
+// longest "@type" string the encode kernel resolves itself
+constexpr uint32_t ANY_URL_MAX = 256;
 
 // ---------------------------------------------------------------------------
 // Device helpers
@@ -197,6 +214,35 @@ DEV uint64_t fnv1a64(const uint8_t* p, uint32_t n) {
 }
 
 DEV int lane_id() { return threadIdx.x & (WAVE - 1); }
+
+// Message index named by an Any type URL, or -1.  The name is what follows
+// the last '/' (the whole string without one; Go and Python protojson agree).
+// A hash hit is CONFIRMED by a lane-strided byte compare of the name: a
+// collision would transcode the payload under the wrong schema.  Wave-uniform.
+DEV int resolve_type_url(const Tables& t, const uint8_t* url, uint32_t n,
+                         int lane) {
+  uint32_t start = 0;
+  for (uint32_t i = 0; i < n; ++i)
+    if (url[i] == '/') start = i + 1;
+  const uint8_t* name = url + start;
+  uint32_t nlen = n - start;
+  uint64_t h = fnv1a64(name, nlen);
+  int lo = 0, hi = t.n_types;  // lower bound over the hash-sorted table
+  while (lo < hi) {
+    int mid = (lo + hi) >> 1;
+    if (t.types[mid].hash < h) lo = mid + 1;
+    else hi = mid;
+  }
+  for (; lo < t.n_types && t.types[lo].hash == h; ++lo) {
+    const TypeEntry& e = t.types[lo];
+    if (e.name_len != nlen) continue;
+    uint32_t bad = 0;
+    for (uint32_t i = (uint32_t)lane; i < nlen; i += WAVE)
+      bad |= (t.names[e.name_off + i] != name[i]);
+    if (__all(!bad)) return e.msg_idx;
+  }
+  return -1;
+}
 
 // wave-uniform broadcast of a value held by lane 0
 DEV uint32_t bcast0_u32(uint32_t v) { return __shfl(v, 0, WAVE); }

@@ -306,7 +306,7 @@ class Engine : public spanapi::ISpanExecutor {
          py::bytes name_blob, int n_msgs, int n_tools, int max_batch,
          size_t cap_in, size_t cap_pb, size_t cap_scratch, size_t cap_final,
          py::object tool_paths, py::object tool_out_msg,
-         py::object tool_backend)
+         py::object tool_backend, py::bytes type_table)
       : device_(device), max_batch_(max_batch) {
     if (!tool_paths.is_none()) {
       for (auto el : tool_paths.cast<py::sequence>())
@@ -365,6 +365,9 @@ class Engine : public spanapi::ISpanExecutor {
     tables_.names = (const uint8_t*)d_names_.p;
     tables_.n_msgs = n_msgs;
     tables_.n_tools = n_tools;
+    upload_blob(type_table, d_types_);
+    tables_.types = (const TypeEntry*)d_types_.p;
+    tables_.n_types = (int32_t)(py::len(type_table) / sizeof(TypeEntry));
 
     d_in_.alloc(cap_in);
     d_resp_.alloc(cap_in);
@@ -1535,7 +1538,8 @@ class Engine : public spanapi::ISpanExecutor {
   hipEvent_t ev_h2d_[PIPE_MAX_CHUNKS] = {};
   hipEvent_t ev_krn_[PIPE_MAX_CHUNKS] = {};
   Tables tables_{};
-  DeviceBuf d_msgs_, d_fields_, d_enums_, d_enum_vals_, d_tools_, d_names_;
+  DeviceBuf d_msgs_, d_fields_, d_enums_, d_enum_vals_, d_tools_, d_names_,
+      d_types_;
   DeviceBuf d_in_, d_resp_, d_scratch_, d_final_;
   DeviceBuf d_rid_, d_dec_results_;
   BufView d_off3_, d_aux2_, d_results_, d_id_slots_, d_pb_;
@@ -1611,7 +1615,7 @@ PYBIND11_MODULE(_jsonproto, m) {
   py::class_<Engine>(m, "Engine")
       .def(py::init<int, py::bytes, py::bytes, py::bytes, py::bytes, py::bytes,
                     py::bytes, int, int, int, size_t, size_t, size_t, size_t,
-                    py::object, py::object, py::object>(),
+                    py::object, py::object, py::object, py::bytes>(),
            py::arg("device"), py::arg("msg_table"), py::arg("field_table"),
            py::arg("enum_table"), py::arg("enum_values"), py::arg("tool_table"),
            py::arg("name_blob"), py::arg("n_msgs"), py::arg("n_tools"),
@@ -1620,7 +1624,8 @@ PYBIND11_MODULE(_jsonproto, m) {
            py::arg("cap_final") = 160u << 20,
            py::arg("tool_paths") = py::none(),
            py::arg("tool_out_msg") = py::none(),
-           py::arg("tool_backend") = py::none())
+           py::arg("tool_backend") = py::none(),
+           py::arg("type_table") = py::bytes())
       .def("encode", &Engine::encode, py::arg("data"), py::arg("in_off"),
            py::arg("pb_off"), py::arg("msg_idx") = py::none(),
            py::arg("mode") = 0, py::arg("max_depth") = 10,

@@ -36,9 +36,10 @@ class HostEngine {
  public:
   HostEngine(py::bytes msg_table, py::bytes field_table, py::bytes enum_table,
              py::bytes enum_values, py::bytes tool_table, py::bytes name_blob,
-             int n_msgs, int n_tools)
+             int n_msgs, int n_tools, py::bytes type_table)
       : msgs_{msg_table}, fields_{field_table}, enums_{enum_table},
-        enum_vals_{enum_values}, tools_{tool_table}, names_{name_blob} {
+        enum_vals_{enum_values}, tools_{tool_table}, names_{name_blob},
+        types_{type_table} {
     t_.msgs = (const MsgEntry*)msgs_.ptr();
     t_.fields = (const FieldEntry*)fields_.ptr();
     t_.enums = (const EnumEntry*)enums_.ptr();
@@ -47,6 +48,8 @@ class HostEngine {
     t_.names = names_.ptr();
     t_.n_msgs = n_msgs;
     t_.n_tools = n_tools;
+    t_.types = (const TypeEntry*)types_.ptr();
+    t_.n_types = (int32_t)(types_.data.size() / sizeof(TypeEntry));
   }
 
   py::tuple encode(py::buffer data, py::array_t<uint32_t> in_off,
@@ -137,7 +140,7 @@ class HostEngine {
     }
   }
 
-  Blob msgs_, fields_, enums_, enum_vals_, tools_, names_;
+  Blob msgs_, fields_, enums_, enum_vals_, tools_, names_, types_;
   Tables t_{};
   std::vector<SlotResult> last_results_;
   std::vector<uint8_t> last_ids_;
@@ -147,7 +150,11 @@ PYBIND11_MODULE(_hostsim, m) {
   m.doc() = "single-lane CPU build of the gfx950 transcode kernels";
   py::class_<HostEngine>(m, "HostEngine")
       .def(py::init<py::bytes, py::bytes, py::bytes, py::bytes, py::bytes,
-                    py::bytes, int, int>())
+                    py::bytes, int, int, py::bytes>(),
+           py::arg("msg_table"), py::arg("field_table"), py::arg("enum_table"),
+           py::arg("enum_values"), py::arg("tool_table"), py::arg("name_blob"),
+           py::arg("n_msgs"), py::arg("n_tools"),
+           py::arg("type_table") = py::bytes())
       .def("encode", &HostEngine::encode, py::arg("data"), py::arg("in_off"),
            py::arg("pb_off"), py::arg("msg_idx") = py::none(),
            py::arg("mode") = 0, py::arg("max_depth") = 10,

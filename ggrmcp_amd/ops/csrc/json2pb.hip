@@ -20,9 +20,10 @@
 // bool, enum (name or number), nested messages, repeated (packed emission),
 // maps (string/int/bool keys), oneof exclusivity, duplicate-key rejection,
 // null handling, and the WKTs Timestamp / Duration / wrappers / Empty /
-// Struct / Value / ListValue / FieldMask.  google.protobuf.Any and >48-byte
-// request ids return E_UNSUPPORTED so the host transcodes those requests
-// (counted, never silent).  Doubles parse with <=1 ulp error outside the
+// Struct / Value / ListValue / FieldMask, and google.protobuf.Any whose
+// "@type" comes first and resolves in the type table (encode_any_value).
+// Other Any shapes and >48-byte request ids return E_UNSUPPORTED so the host
+// transcodes those requests (counted, never silent).  Doubles parse with <=1 ulp error outside the
 // exact fast path (|exp|<=22, mantissa<2^53).
 
 #include "common.h"
@@ -1343,6 +1344,108 @@ DEVN bool encode_map_entry_key(Ctx& c, const FieldEntry& f, const FieldEntry& kf
   }
 }
 
+// google.protobuf.Any field value (tag NOT yet emitted; same return contract
+// as encode_msgfield_value).  Device shape: an object whose FIRST member is
+// "@type" with an unescaped string of at most ANY_URL_MAX bytes.  A plain
+// message payload (Empty is one to the oracle) continues as an EM_BODY frame
+// of the resolved type, entered after the comma that follows "@type" — the
+// remaining members ARE the payload's fields, and a second "@type" falls out
+// as an unknown field.  Timestamp/Duration/FieldMask/wrappers take
+// `,"value":X}` through the WKT emitters.  Everything else leaves with
+// E_UNSUPPORTED (docs/KERNELS.md, host-escape rules).
+DEVN int encode_any_value(Ctx& c, const FieldEntry& f, uint8_t* push_mode,
+                          int32_t* push_idx, uint32_t* slots,
+                          uint8_t* n_slots) {
+  if (!emit_tag(c, f.number, W_LEN)) return 0;
+  uint32_t oslot;
+  if (!reserve_len(c, &oslot)) return 0;
+  if (!expect(c, '{')) return 0;
+  skip_ws(c);
+  if (peek(c) == '}') {  // {} is the empty Any
+    c.pos++;
+    return backfill_len(c, oslot) ? 1 : 0;
+  }
+  uint32_t st, rl;
+  bool esc;
+  if (!string_span(c, &st, &rl, &esc)) return 0;
+  if (esc || rl != 5 || !wave_equal(c, c.s + st, (const uint8_t*)"@type", 5)) {
+    fail(c, E_UNSUPPORTED);
+    return 0;
+  }
+  if (!expect(c, ':')) return 0;
+  if (!string_span(c, &st, &rl, &esc)) return 0;
+  if (esc || rl > ANY_URL_MAX) {
+    fail(c, E_UNSUPPORTED);
+    return 0;
+  }
+  if (!emit_tag(c, 1, W_LEN)) return 0;
+  if (!encode_string_payload(c, st, rl, false)) return 0;
+  int midx = resolve_type_url(c.t, c.s + st, rl, c.lane);
+  if (midx < 0) {  // the host re-attempt surfaces the real error text
+    fail(c, E_UNSUPPORTED);
+    return 0;
+  }
+  const MsgEntry& pm = c.t.msgs[midx];
+  int32_t wkt = pm.wkt_kind;
+  if (wkt == WKT_STRUCT || wkt == WKT_VALUE || wkt == WKT_LISTVALUE ||
+      wkt == WKT_ANY) {
+    fail(c, E_UNSUPPORTED);
+    return 0;
+  }
+  skip_ws(c);
+  if (wkt == WKT_NONE || wkt == WKT_EMPTY) {
+    if (peek(c) == '}') {  // type_url only: no value field
+      c.pos++;
+      return backfill_len(c, oslot) ? 1 : 0;
+    }
+    if (!expect(c, ',')) return 0;
+    skip_ws(c);
+    if (peek(c) != '"') {  // the pushed frame must start at a member key
+      fail(c, E_PARSE);
+      return 0;
+    }
+    if (!emit_tag(c, 2, W_LEN)) return 0;
+    uint32_t islot;
+    if (!reserve_len(c, &islot)) return 0;
+    *push_mode = EM_BODY;
+    *push_idx = midx;
+    slots[0] = islot;
+    slots[1] = oslot;
+    *n_slots = 2;
+    return 2;
+  }
+  // scalar-like WKT payload: exactly `,"value":X}` (the oracle also takes
+  // other member orders and ignores extra members: those go to the host)
+  if (peek(c) != ',') {
+    fail(c, E_UNSUPPORTED);
+    return 0;
+  }
+  c.pos++;
+  if (!string_span(c, &st, &rl, &esc)) return 0;
+  if (esc || rl != 5 || !wave_equal(c, c.s + st, (const uint8_t*)"value", 5)) {
+    fail(c, E_UNSUPPORTED);
+    return 0;
+  }
+  if (!expect(c, ':')) return 0;
+  skip_ws(c);
+  if (!emit_tag(c, 2, W_LEN)) return 0;
+  uint32_t islot;
+  if (!reserve_len(c, &islot)) return 0;
+  bool ok;
+  if (wkt == WKT_WRAPPER) ok = encode_scalar_field(c, c.t.fields[pm.field_start]);
+  else if (wkt == WKT_FIELDMASK) ok = encode_fieldmask_payload(c, f.number);
+  else ok = encode_tsdur_payload(c, wkt == WKT_TIMESTAMP, f.number);
+  if (!ok) return 0;
+  if (!backfill_len(c, islot)) return 0;
+  skip_ws(c);
+  if (peek(c) != '}') {
+    fail(c, E_UNSUPPORTED);
+    return 0;
+  }
+  c.pos++;
+  return backfill_len(c, oslot) ? 1 : 0;
+}
+
 // message-typed field value (tag NOT yet emitted).  Leaf WKTs complete
 // inline (returns 1).  Container bodies emit tag + slot(s), consume the
 // opening brace/bracket and return 2 with push parameters.  0 = error.
@@ -1423,7 +1526,7 @@ DEVN int encode_msgfield_value(Ctx& c, const FieldEntry& f, uint8_t* push_mode,
       return 2;
     }
     case WKT_ANY:
-      return fail(c, E_UNSUPPORTED) ? 1 : 0;
+      return encode_any_value(c, f, push_mode, push_idx, slots, n_slots);
     default: {  // plain nested message
       if (!emit_tag(c, f.number, W_LEN)) return 0;
       uint32_t slot;
@@ -1599,6 +1702,9 @@ DEV bool encode_walk(Ctx& c, int top_msg_idx, int wg_item = 0,
       if (!expect(c, '{')) return false;
       skip_ws(c);
       return expect(c, '}');
+    } else if (m.wkt_kind == WKT_ANY) {
+      // a tool whose message is itself an Any: the host transcodes
+      return fail(c, E_UNSUPPORTED);
     } else {
       if (!expect(c, '{')) return false;
       skip_ws(c);

@@ -15,9 +15,10 @@
 // "Ns" forms with 3-digit-group nano trimming, wrappers unwrapped,
 // Struct/Value/ListValue as raw JSON, Empty as {}.  Fields are emitted in
 // wire order with adjacent-occurrence grouping for repeated/map fields;
-// out-of-order wire (no real serializer produces it) and google.protobuf.Any
-// flag E_UNSUPPORTED so the host transcodes that request (counted, never
-// silent).  Doubles print as 17-significant-digit shortest-trimmed decimals
+// out-of-order wire (no real serializer produces it) flags E_UNSUPPORTED so
+// the host transcodes that request (counted, never silent).
+// google.protobuf.Any prints on the device when its wire is [type_url]
+// [value] and the URL resolves in the type table (decode_any_head).  Doubles print as 17-significant-digit shortest-trimmed decimals
 // (value-exact round trip; not always the minimal digit string).
 
 #include "common.h"
@@ -1060,10 +1061,66 @@ struct DFrame {
 DEVN bool map_entry_step(DCtx& c, DFrame& f, uint32_t eend, DFrame* stack,
                         int& sp, int* pushed);
 
+// google.protobuf.Any body at c.pos..vend.  Device wire shapes: empty,
+// [type_url], [type_url][value] — in that order, each once, nothing else;
+// every other wire (Python accepts value-before-url, for one) leaves with
+// E_UNSUPPORTED.  Returns 1 when the whole Any is printed (empty, or a
+// Timestamp/Duration/FieldMask/wrapper payload as `,"value":X}`), 0 on
+// error, and 3 for a plain message payload (Empty is one to the oracle):
+// `{"@type":"..."` is already out, and the caller pushes an FM_BODY frame
+// over the value bytes with first_member CLEARED and no opening brace, so
+// the members continue after a comma and the frame's brace closes the Any.
+DEVN int decode_any_head(DCtx& c, uint32_t vend, int32_t* push_idx,
+                         uint32_t* body_end) {
+  if (c.pos >= vend) return puts_(c, "{}", 2) ? 1 : 0;
+  if (c.pb[c.pos] != ((1u << 3) | W_LEN)) return dfail(c, E_UNSUPPORTED) ? 1 : 0;
+  c.pos++;
+  uint64_t ulen;
+  if (!read_varint(c, &ulen)) return 0;
+  if (c.pos > vend || ulen > vend - c.pos) return dfail(c, E_PARSE) ? 1 : 0;
+  const uint8_t* url = c.pb + c.pos;
+  c.pos += (uint32_t)ulen;
+  int midx = resolve_type_url(c.t, url, (uint32_t)ulen, c.lane);
+  // unresolved: the host re-attempt surfaces the real error text
+  if (midx < 0) return dfail(c, E_UNSUPPORTED) ? 1 : 0;
+  const MsgEntry& pm = c.t.msgs[midx];
+  int32_t wkt = pm.wkt_kind;
+  if (wkt == WKT_STRUCT || wkt == WKT_VALUE || wkt == WKT_LISTVALUE ||
+      wkt == WKT_ANY)
+    return dfail(c, E_UNSUPPORTED) ? 1 : 0;
+  if (c.pos < vend) {
+    if (c.pb[c.pos] != ((2u << 3) | W_LEN)) return dfail(c, E_UNSUPPORTED) ? 1 : 0;
+    c.pos++;
+    uint64_t vlen;
+    if (!read_varint(c, &vlen)) return 0;
+    if (c.pos > vend || vlen > vend - c.pos) return dfail(c, E_PARSE) ? 1 : 0;
+    // anything after the value (a second url, an unknown field): host
+    if (vlen != vend - c.pos) return dfail(c, E_UNSUPPORTED) ? 1 : 0;
+  }
+  uint32_t vpos = c.pos;  // value bytes are vpos..vend (empty without field 2)
+  if (!puts_(c, "{\"@type\":", 9)) return 0;
+  if (!put_json_string(c, url, (uint32_t)ulen)) return 0;
+  c.pos = vpos;
+  if (wkt == WKT_NONE || wkt == WKT_EMPTY) {
+    *push_idx = midx;
+    *body_end = vend;
+    return 3;
+  }
+  if (!puts_(c, ",\"value\":", 9)) return 0;
+  bool ok;
+  if (wkt == WKT_WRAPPER) ok = decode_wrapper_body(c, pm, vend);
+  else if (wkt == WKT_FIELDMASK) ok = decode_fieldmask_body(c, vend);
+  else ok = decode_ts_dur_body(c, vend, wkt == WKT_TIMESTAMP);
+  if (!ok) return 0;
+  return putc_(c, '}') ? 1 : 0;
+}
+
 
 // classify field f's message body starting at c.pos with length vlen.
 // Scalar WKTs are emitted inline (returns 1=done), container bodies are
 // described for a push (returns 2) with *push_mode set; error -> 0.
+// 3 = the plain-message payload of an Any (see decode_any_head): a push
+// like 2, but the opening brace and the first member are already printed.
 DEVN int enter_body(DCtx& c, int msg_idx, uint32_t vend, uint8_t* push_mode,
                    int32_t* push_idx, uint32_t* body_end) {
   *push_idx = msg_idx;
@@ -1079,7 +1136,8 @@ DEVN int enter_body(DCtx& c, int msg_idx, uint32_t vend, uint8_t* push_mode,
     case WKT_FIELDMASK:
       return decode_fieldmask_body(c, vend) ? 1 : 0;
     case WKT_ANY:
-      return dfail(c, E_UNSUPPORTED) ? 1 : 0;
+      *push_mode = FM_BODY;
+      return decode_any_head(c, vend, push_idx, body_end);
     case WKT_VALUE: {
       // one-shot oneof; nested struct/list push frames
       if (c.pos >= vend) return puts_(c, "null", 4) ? 1 : 0;
@@ -1191,10 +1249,10 @@ DEVN bool map_entry_step(DCtx& c, DFrame& f, uint32_t eend, DFrame* stack,
               nf.cont_field = -1;
               nf.cont_num = 0;
               nf.mode = pm;
-              nf.first_member = 1;
+              nf.first_member = r != 3;
               nf.cont_kind = CK_NONE;
               nf.cont_first = 1;
-              if (!putc_(c, pm == FM_LIST ? '[' : '{')) return false;
+              if (r != 3 && !putc_(c, pm == FM_LIST ? '[' : '{')) return false;
               *pushed = 1;
               return true;
             }
@@ -1263,10 +1321,10 @@ DEVN bool map_entry_step(DCtx& c, DFrame& f, uint32_t eend, DFrame* stack,
     nf.cont_field = -1;
     nf.cont_num = 0;
     nf.mode = pm;
-    nf.first_member = 1;
+    nf.first_member = r != 3;
     nf.cont_kind = CK_NONE;
     nf.cont_first = 1;
-    if (!putc_(c, pm == FM_LIST ? '[' : '{')) return false;
+    if (r != 3 && !putc_(c, pm == FM_LIST ? '[' : '{')) return false;
     *pushed = 1;
     return true;
   }
@@ -1303,6 +1361,8 @@ DEV bool decode_walk(DCtx& c, int top_msg_idx, uint32_t top_end,
     uint8_t pm = FM_BODY;
     int32_t pidx = top_msg_idx;
     uint32_t bend = top_end;
+    // a tool whose message is itself an Any: the host transcodes
+    if (c.t.msgs[top_msg_idx].wkt_kind == WKT_ANY) return dfail(c, E_UNSUPPORTED);
     int r = enter_body(c, top_msg_idx, top_end, &pm, &pidx, &bend);
     if (r == 0) return false;
     if (r == 1) return c.status == E_OK;
@@ -1384,10 +1444,10 @@ DEV bool decode_walk(DCtx& c, int top_msg_idx, uint32_t top_end,
         nf.cont_field = -1;
         nf.cont_num = 0;
         nf.mode = pm;
-        nf.first_member = 1;
+        nf.first_member = r != 3;
         nf.cont_kind = CK_NONE;
         nf.cont_first = 1;
-        if (!putc_(c, pm == FM_LIST ? '[' : '{')) return false;
+        if (r != 3 && !putc_(c, pm == FM_LIST ? '[' : '{')) return false;
         continue;
       }
       if (wt != expected_wire(fe)) return dfail(c, E_PARSE);
@@ -1469,10 +1529,10 @@ DEV bool decode_walk(DCtx& c, int top_msg_idx, uint32_t top_end,
       nf.cont_field = -1;
       nf.cont_num = 0;
       nf.mode = pm;
-      nf.first_member = 1;
+      nf.first_member = r != 3;
       nf.cont_kind = CK_NONE;
       nf.cont_first = 1;
-      if (!putc_(c, pm == FM_LIST ? '[' : '{')) return false;
+      if (r != 3 && !putc_(c, pm == FM_LIST ? '[' : '{')) return false;
       continue;
     }
     if (f.mode == FM_STRUCT) {
@@ -1505,6 +1565,9 @@ DEV bool decode_walk(DCtx& c, int top_msg_idx, uint32_t top_end,
 
     // FM_BODY
     if (c.pos >= f.end) {
+      // a field that runs past its message (an Any payload cut short, say)
+      // must not hand the parent a cursor inside its next field
+      if (c.pos > f.end) return dfail(c, E_PARSE);
       if (!(bare_top && sp == 1) && !putc_(c, '}')) return false;
       --sp;
       continue;
@@ -1625,10 +1688,10 @@ DEV bool decode_walk(DCtx& c, int top_msg_idx, uint32_t top_end,
         nf.cont_field = -1;
         nf.cont_num = 0;
         nf.mode = pm;
-        nf.first_member = 1;
+        nf.first_member = r != 3;
         nf.cont_kind = CK_NONE;
         nf.cont_first = 1;
-        if (!putc_(c, pm == FM_LIST ? '[' : '{')) return false;
+        if (r != 3 && !putc_(c, pm == FM_LIST ? '[' : '{')) return false;
         continue;
       }
       if (wt != expected_wire(*fe)) return dfail(c, E_PARSE);
@@ -1660,10 +1723,10 @@ DEV bool decode_walk(DCtx& c, int top_msg_idx, uint32_t top_end,
       nf.cont_field = -1;
       nf.cont_num = 0;
       nf.mode = pm;
-      nf.first_member = 1;
+      nf.first_member = r != 3;
       nf.cont_kind = CK_NONE;
       nf.cont_first = 1;
-      if (!putc_(c, pm == FM_LIST ? '[' : '{')) return false;
+      if (r != 3 && !putc_(c, pm == FM_LIST ? '[' : '{')) return false;
       continue;
     }
     if (wt != expected_wire(*fe)) return dfail(c, E_PARSE);

@@ -117,5 +117,10 @@ class NativeWireClient:
     def healthy(self) -> bool:
         return self._cli.healthy()
 
+    def stats(self) -> Dict[str, int]:
+        """Transport counters (calls, batches, send_calls, send_bytes,
+        recv_calls, wake_writes, notifies) since the client was created."""
+        return dict(self._cli.stats())
+
     def close(self) -> None:
         self._cli.close()

@@ -35,6 +35,7 @@
 #include <stdlib.h>
 #include <sys/eventfd.h>
 #include <sys/socket.h>
+#include <sys/uio.h>
 #include <sys/un.h>
 #include <unistd.h>
 
@@ -132,16 +133,97 @@ static nghttp2_nv nv(const std::string& name, const std::string& value) {
   return NV(name.data(), value.data(), name.size(), value.size());
 }
 
-// grpc message framing
+// grpc message framing: 5-byte prefix + payload written straight into `out`
+// (one allocation, one copy of the wire)
+static void grpc_frame_into(std::string& out, const void* payload, size_t len) {
+  out.resize(5 + len);
+  out[0] = 0;
+  uint32_t n = htonl((uint32_t)len);
+  memcpy(&out[1], &n, 4);
+  if (len) memcpy(&out[5], payload, len);
+}
 static std::string grpc_frame(const std::string& payload) {
   std::string out;
-  out.resize(5 + payload.size());
-  out[0] = 0;
-  uint32_t n = htonl((uint32_t)payload.size());
-  memcpy(&out[1], &n, 4);
-  memcpy(&out[5], payload.data(), payload.size());
+  grpc_frame_into(out, payload.data(), payload.size());
   return out;
 }
+
+// Transport counters (relaxed atomics; read with stats()).  They make the
+// syscall / wake-up shape of the transport checkable without timing anything.
+// The macro lets tools/h2_probe.cpp also build against a header from before
+// the counters existed, for before/after runs.
+#define GGRMCP_H2_STATS 1
+struct TransportStats {
+  std::atomic<uint64_t> calls{0};        // unary/stream calls submitted
+  std::atomic<uint64_t> batches{0};      // invoke_* batches
+  std::atomic<uint64_t> send_calls{0};   // send()/sendmsg() syscalls
+  std::atomic<uint64_t> send_bytes{0};
+  std::atomic<uint64_t> recv_calls{0};   // recv() syscalls
+  std::atomic<uint64_t> wake_writes{0};  // eventfd writes
+  std::atomic<uint64_t> notifies{0};     // condvar notifies
+  static void bump(std::atomic<uint64_t>& c, uint64_t v = 1) {
+    c.fetch_add(v, std::memory_order_relaxed);
+  }
+  void add_into(std::unordered_map<std::string, uint64_t>& m) const {
+    auto ld = [](const std::atomic<uint64_t>& c) {
+      return c.load(std::memory_order_relaxed);
+    };
+    m["calls"] += ld(calls);
+    m["batches"] += ld(batches);
+    m["send_calls"] += ld(send_calls);
+    m["send_bytes"] += ld(send_bytes);
+    m["recv_calls"] += ld(recv_calls);
+    m["wake_writes"] += ld(wake_writes);
+    m["notifies"] += ld(notifies);
+  }
+};
+
+// Gathered flush (flush_session): small frames are copied into the
+// connection's write buffer until it holds H2_GATHER_CAP bytes, then go out
+// in ONE send().  A frame of H2_DIRECT_SEND_MIN bytes or more is never
+// copied: it is sent from nghttp2's own buffer, in the same syscall as
+// whatever was gathered before it (sendmsg, two iovecs), and it switches the
+// connection to bulk mode, in which every frame is sent as it comes, one
+// send() each, until a whole flush pass has seen no such frame.  Gathering
+// pays where frames are small (a 1 KB unary call is three of ~1 KB or less);
+// 64 KB payloads travel as runs of 16 KB + 9 DATA frames (nghttp2's DATA
+// frame size, whatever MAX_FRAME_SIZE the peer announces), and holding those
+// back measured slower than sending each at once, which lets the peer read
+// while the next frame is packed (profiles/h2_coalesce.md).
+#ifndef H2_GATHER_CAP
+#define H2_GATHER_CAP (256u << 10)
+#endif
+#ifndef H2_DIRECT_SEND_MIN
+#define H2_DIRECT_SEND_MIN (8u << 10)
+#endif
+static constexpr size_t kGatherCap = H2_GATHER_CAP;
+static constexpr size_t kDirectSendMin = H2_DIRECT_SEND_MIN;
+// Bulk mode outlives the pass that saw the big frame by this many passes of
+// small frames only, so the HEADERS of the next large batch (their own pass,
+// or the head of one) are not held back either.
+static constexpr int kBulkHoldPasses = 8;
+
+// Batch placement: a batch is laid on the connections in contiguous runs of
+// up to this many calls (start connection rotates per batch).  1 = rotated
+// striping, one call per connection in turn.  GGRMCP_H2_RUN overrides.
+static constexpr int kDefaultConnRun = 1;
+static int transport_conn_run() {
+  static const int v = [] {
+    const char* e = getenv("GGRMCP_H2_RUN");
+    int k = e ? atoi(e) : kDefaultConnRun;
+    return k < 1 ? 1 : k;
+  }();
+  return v;
+}
+
+// connection write buffer: bytes [off, buf.size()) are still unsent
+struct WriteBuf {
+  std::string buf;
+  size_t off = 0;
+  int bulk = 0;  // > 0: bulk mode (no gathering); set to kBulkHoldPasses by a
+                 // big frame, worn off by passes that send only small ones
+  size_t pending() const { return buf.size() - off; }
+};
 
 // protobuf wire walk: validates structure, returns false on malformed input
 static bool pb_validate(const uint8_t* p, size_t len) {
@@ -246,19 +328,27 @@ static bool parse_hello_name(const uint8_t* p, size_t len, std::string* name) {
   return true;
 }
 
-static std::string make_hello_response(const std::string& name) {
-  std::string msg = "Hello, " + name + "!";
-  std::string out;
-  out.push_back('\x0a');  // field 1, wire 2
-  // varint length
-  uint64_t v = msg.size();
-  while (v >= 0x80) {
-    out.push_back((char)(v | 0x80));
-    v >>= 7;
+// grpc-framed HelloResponse{message = "Hello, <name>!"}, built in place
+static void hello_response_into(std::string& out, const std::string& name) {
+  size_t mlen = 7 + name.size() + 1;
+  char var[10];
+  size_t nvar = 0;
+  for (uint64_t v = mlen;; v >>= 7) {
+    if (v >= 0x80) { var[nvar++] = (char)(v | 0x80); }
+    else { var[nvar++] = (char)v; break; }
   }
-  out.push_back((char)v);
-  out += msg;
-  return out;
+  size_t pblen = 1 + nvar + mlen;
+  out.resize(5 + pblen);
+  char* p = &out[0];
+  *p++ = 0;
+  uint32_t be = htonl((uint32_t)pblen);
+  memcpy(p, &be, 4); p += 4;
+  *p++ = '\x0a';  // field 1, wire 2
+  memcpy(p, var, nvar); p += nvar;
+  memcpy(p, "Hello, ", 7); p += 7;
+  if (!name.empty()) memcpy(p, name.data(), name.size());
+  p += name.size();
+  *p = '!';
 }
 
 // ---------------------------------------------------------------------------
@@ -283,15 +373,26 @@ struct Call {
 
 // One submitted batch.  Shared ownership between the caller and the
 // connection threads so an early (deadline) return never leaves dangling
-// pointers; completion is signalled via the batch's cv.
+// pointers; completion is signalled via the batch's cv — once, by whichever
+// call completes last (the waiter has nothing to do before that, and its
+// deadline is a timed wait, so it needs no intermediate wake-ups).
 struct Batch {
   std::deque<Call> calls;   // deque: stable addresses
   std::mutex mu;
   std::condition_variable cv;
   std::atomic<int> done{0};
+  int total = 0;            // set before any call is queued
+  TransportStats* stats = nullptr;
   void complete_one() {
-    { std::lock_guard<std::mutex> lk(mu); done.fetch_add(1); }
-    cv.notify_one();
+    bool last;
+    {
+      std::lock_guard<std::mutex> lk(mu);
+      last = done.fetch_add(1) + 1 >= total;
+    }
+    if (last) {
+      if (stats) TransportStats::bump(stats->notifies);
+      cv.notify_one();
+    }
   }
 };
 
@@ -308,8 +409,14 @@ struct ClientConn {
   std::mutex mu;
   std::deque<QueuedCall> pending;              // submitted by callers
   std::unordered_map<int32_t, QueuedCall> live;
-  std::string wbuf;                    // partial write buffer
+  WriteBuf wbuf;                       // gathered / partially sent frames
+  TransportStats stats;                // this connection's send/recv counts
   std::atomic<bool> stop{false};
+  // true while the thread is (about to be) blocked in poll: only then does
+  // a submitter need to write wake_fd.  The thread re-checks `pending`
+  // under `mu` after raising it, so a call queued in between is never
+  // left waiting for the poll timeout.
+  std::atomic<bool> sleeping{false};
   std::atomic<int> inflight{0};
   int max_inflight = 512;  // streams submitted concurrently per connection
   size_t max_resp = 0;     // unary response byte cap (0 = unlimited);
@@ -330,27 +437,41 @@ static ssize_t client_data_read(nghttp2_session*, int32_t stream_id, uint8_t* bu
   return (ssize_t)n;
 }
 
+// atoi() over a header value that is not NUL-terminated: optional blanks and
+// sign, then digits; anything else ends the number (no digits = 0)
+static int parse_status(const uint8_t* v, size_t n) {
+  size_t i = 0;
+  while (i < n && (v[i] == ' ' || (v[i] >= '\t' && v[i] <= '\r'))) ++i;
+  bool neg = false;
+  if (i < n && (v[i] == '-' || v[i] == '+')) neg = v[i++] == '-';
+  int r = 0;
+  for (; i < n && v[i] >= '0' && v[i] <= '9' && r < 100000000; ++i)
+    r = r * 10 + (v[i] - '0');
+  return neg ? -r : r;
+}
+
 static int client_on_header(nghttp2_session* sess, const nghttp2_frame* frame,
                             const uint8_t* name, size_t namelen, const uint8_t* value,
                             size_t valuelen, uint8_t, void* user) {
-  ClientConn* conn = (ClientConn*)user;
-  auto it = conn->live.find(frame->hd.stream_id);
-  if (it == conn->live.end()) return 0;
+  (void)user;
+  // The Call is the stream's user data (set at submit; nghttp2 returns null
+  // once the stream is closed, which is also when `live` drops it).
+  Call* call =
+      (Call*)nghttp2_session_get_stream_user_data(sess, frame->hd.stream_id);
+  if (!call) return 0;
   if (namelen == 11 && memcmp(name, "grpc-status", 11) == 0) {
-    it->second.call->grpc_status =
-        atoi(std::string((const char*)value, valuelen).c_str());
+    call->grpc_status = parse_status(value, valuelen);
   } else if (namelen == 12 && memcmp(name, "grpc-message", 12) == 0) {
-    it->second.call->grpc_message.assign((const char*)value, valuelen);
+    call->grpc_message.assign((const char*)value, valuelen);
   }
   return 0;
 }
 
-static int client_on_data(nghttp2_session*, uint8_t, int32_t stream_id,
+static int client_on_data(nghttp2_session* sess, uint8_t, int32_t stream_id,
                           const uint8_t* data, size_t len, void* user) {
   ClientConn* conn = (ClientConn*)user;
-  auto it = conn->live.find(stream_id);
-  if (it != conn->live.end()) {
-    Call* c = it->second.call;
+  Call* c = (Call*)nghttp2_session_get_stream_user_data(sess, stream_id);
+  if (c) {
     if (!c->no_cap && conn->max_resp &&
         c->response.size() + len > conn->max_resp) {
       // cap ONE oversized unary response without failing the whole batch
@@ -368,7 +489,7 @@ static int client_on_stream_close(nghttp2_session*, int32_t stream_id, uint32_t,
   ClientConn* conn = (ClientConn*)user;
   auto it = conn->live.find(stream_id);
   if (it != conn->live.end()) {
-    QueuedCall qc = it->second;
+    QueuedCall qc = std::move(it->second);
     conn->live.erase(it);
     qc.call->done.store(true, std::memory_order_release);
     conn->inflight.fetch_sub(1);
@@ -386,36 +507,96 @@ static void fail_call(ClientConn* conn, QueuedCall& qc, int status,
 }
 
 
-// Pump nghttp2 output to the socket until the session has nothing more to
-// send or the socket blocks.  Returns false on fatal socket error; *blocked
-// is set when the socket is full (caller arms POLLOUT).  The subtle case
-// this exists for: a partial send() followed by a successful wbuf drain must
-// LOOP BACK into nghttp2_session_mem_send — stopping there leaves queued
-// frames unsent with nothing to wake the poll (observed as ~2 poll-timeout
-// stalls per 1024-batch over UDS: 205 ms/batch instead of 7).
-static bool flush_session(nghttp2_session* sess, int fd, std::string& wbuf,
-                          bool* blocked) {
-  *blocked = false;
+// Send the unsent part of `wb`, then `extra` (a frame still owned by
+// nghttp2; may be null), in as few syscalls as the socket allows: one when
+// it takes everything.  Returns 1 when all of it went out (wb is then
+// empty), 0 when the socket is full (what is left, `extra`'s remainder
+// included, is owned by wb), -1 on a fatal socket error.
+static int wb_send(int fd, WriteBuf& wb, const uint8_t* extra, size_t xn,
+                   TransportStats* st) {
   while (true) {
-    if (!wbuf.empty()) {
-      ssize_t w = send(fd, wbuf.data(), wbuf.size(), MSG_NOSIGNAL);
-      if (w < 0) {
-        if (errno == EAGAIN || errno == EWOULDBLOCK) { *blocked = true; return true; }
-        return false;
-      }
-      wbuf.erase(0, (size_t)w);
-      if (!wbuf.empty()) continue;
+    size_t pend = wb.pending();
+    if (pend == 0) {
+      wb.buf.clear();
+      wb.off = 0;
+      if (xn == 0) return 1;
     }
-    const uint8_t* out = nullptr;
-    ssize_t n = nghttp2_session_mem_send(sess, &out);
-    if (n < 0) return false;
-    if (n == 0) return true;
-    ssize_t w = send(fd, out, (size_t)n, MSG_NOSIGNAL);
+    ssize_t w;
+    if (xn == 0) {
+      w = send(fd, wb.buf.data() + wb.off, pend, MSG_NOSIGNAL);
+    } else if (pend == 0) {
+      w = send(fd, extra, xn, MSG_NOSIGNAL);
+    } else {
+      iovec iov[2] = {{(void*)(wb.buf.data() + wb.off), pend},
+                      {(void*)extra, xn}};
+      msghdr mh{};
+      mh.msg_iov = iov;
+      mh.msg_iovlen = 2;
+      w = sendmsg(fd, &mh, MSG_NOSIGNAL);
+    }
+    TransportStats::bump(st->send_calls);
     if (w < 0) {
-      if (errno == EAGAIN || errno == EWOULDBLOCK) w = 0;
-      else return false;
+      if (errno == EINTR) continue;
+      if (errno == EAGAIN || errno == EWOULDBLOCK) {
+        if (xn) wb.buf.append((const char*)extra, xn);
+        return 0;
+      }
+      return -1;
     }
-    if (w < n) wbuf.assign((const char*)out + w, (size_t)(n - w));
+    TransportStats::bump(st->send_bytes, (uint64_t)w);
+    size_t from_buf = (size_t)w < pend ? (size_t)w : pend;
+    wb.off += from_buf;
+    extra += (size_t)w - from_buf;
+    xn -= (size_t)w - from_buf;
+  }
+}
+
+// Pump nghttp2 output to the socket until the session has nothing more to
+// send or the socket blocks.  Frames are gathered (see H2_GATHER_CAP above)
+// so a batch of small HEADERS/DATA/trailer frames costs one send(), not one
+// each.  The pointer nghttp2_session_mem_send hands out is valid only until
+// the next call, so gathered frames are copied; frames of H2_DIRECT_SEND_MIN
+// bytes or more are sent from nghttp2's own buffer and put the connection
+// into bulk mode (WriteBuf::bulk), where nothing is gathered.
+// Returns false on fatal socket error; *blocked is set when the socket is
+// full (caller arms POLLOUT).  The subtle case this exists for: a partial
+// send() followed by a successful wbuf drain must LOOP BACK into
+// nghttp2_session_mem_send — stopping there leaves queued frames unsent
+// with nothing to wake the poll (observed as ~2 poll-timeout stalls per
+// 1024-batch over UDS: 205 ms/batch instead of 7).  Here every pass starts
+// by draining wbuf and only returns unblocked once mem_send yields nothing.
+static bool flush_session(nghttp2_session* sess, int fd, WriteBuf& wb,
+                          bool* blocked, TransportStats* st) {
+  *blocked = false;
+  bool sent_any = false, saw_big = false;
+  while (true) {
+    int r = wb_send(fd, wb, nullptr, 0, st);
+    if (r < 0) return false;
+    if (r == 0) { *blocked = true; return true; }
+    // wb is empty: gather, or in bulk mode send frame by frame
+    while (wb.buf.size() < kGatherCap) {
+      const uint8_t* out = nullptr;
+      ssize_t n = nghttp2_session_mem_send(sess, &out);
+      if (n < 0) return false;
+      if (n == 0) {
+        if (!wb.buf.empty()) break;
+        // a pass that sent only small frames wears bulk mode off
+        if (sent_any && !saw_big && wb.bulk > 0) --wb.bulk;
+        return true;
+      }
+      sent_any = true;
+      if ((size_t)n >= kDirectSendMin) {
+        saw_big = true;
+        wb.bulk = kBulkHoldPasses;
+      }
+      if (wb.bulk > 0) {
+        r = wb_send(fd, wb, out, (size_t)n, st);
+        if (r < 0) return false;
+        if (r == 0) { *blocked = true; return true; }
+        continue;
+      }
+      wb.buf.append((const char*)out, (size_t)n);
+    }
   }
 }
 
@@ -426,28 +607,38 @@ static void conn_loop(ClientConn* conn) {
       std::lock_guard<std::mutex> lk(conn->mu);
       while (!conn->pending.empty() &&
              conn->inflight.load() < conn->max_inflight) {
-        QueuedCall qc = conn->pending.front();
+        QueuedCall qc = std::move(conn->pending.front());
         Call* call = qc.call;
         conn->pending.pop_front();
-        std::vector<nghttp2_nv> nva;
-        nva.reserve(8 + call->metadata.size());
-        nva.push_back(nv(":method", "POST"));
-        nva.push_back(nv(":scheme", "http"));
-        nva.push_back(nv(":path", call->path));
-        nva.push_back(nv(":authority", conn->authority));
-        nva.push_back(nv("te", "trailers"));
-        nva.push_back(nv("content-type", "application/grpc"));
-        for (auto& kv : call->metadata) nva.push_back(nv(kv.first, kv.second));
+        // fixed request headers live on the stack; only calls that carry
+        // metadata pay for a heap vector
+        nghttp2_nv fixed[6] = {
+            NV(":method", "POST", 7, 4),
+            NV(":scheme", "http", 7, 4),
+            nv(":path", call->path),
+            nv(":authority", conn->authority),
+            NV("te", "trailers", 2, 8),
+            NV("content-type", "application/grpc", 12, 16),
+        };
+        const nghttp2_nv* nva = fixed;
+        size_t nvlen = 6;
+        std::vector<nghttp2_nv> with_md;
+        if (!call->metadata.empty()) {
+          with_md.assign(fixed, fixed + 6);
+          for (auto& kv : call->metadata) with_md.push_back(nv(kv.first, kv.second));
+          nva = with_md.data();
+          nvlen = with_md.size();
+        }
         nghttp2_data_provider prd;
         prd.source.ptr = call;
         prd.read_callback = client_data_read;
-        int32_t sid = nghttp2_submit_request(conn->sess, nullptr, nva.data(),
-                                             nva.size(), &prd, call);
+        int32_t sid = nghttp2_submit_request(conn->sess, nullptr, nva, nvlen,
+                                             &prd, call);
         if (sid < 0) {
           fail_call(conn, qc, 14, "submit failed");  // UNAVAILABLE
           continue;
         }
-        conn->live[sid] = qc;
+        conn->live[sid] = std::move(qc);
         conn->inflight.fetch_add(1);
       }
     }
@@ -465,15 +656,33 @@ static void conn_loop(ClientConn* conn) {
     }
     // write
     bool write_blocked = false;
-    if (!flush_session(conn->sess, conn->fd, conn->wbuf, &write_blocked))
+    if (!flush_session(conn->sess, conn->fd, conn->wbuf, &write_blocked,
+                       &conn->stats))
       conn->broken = true;
     if (conn->broken) break;
 
+    // Going to sleep: raise the flag FIRST, then look at `pending` once more
+    // under the lock.  A submitter pushes under the same lock and reads the
+    // flag afterwards, so either it sees the flag (and writes wake_fd, which
+    // poll then reports) or this check sees its call.
+    conn->sleeping.store(true, std::memory_order_seq_cst);
+    {
+      std::lock_guard<std::mutex> lk(conn->mu);
+      if (!conn->pending.empty() &&
+          conn->inflight.load() < conn->max_inflight) {
+        conn->sleeping.store(false, std::memory_order_relaxed);
+        continue;
+      }
+    }
     pollfd fds[2];
     fds[0] = {conn->fd, (short)(POLLIN | (write_blocked ? POLLOUT : 0)), 0};
     fds[1] = {conn->wake_fd, POLLIN, 0};
     int rc = poll(fds, 2, 100);
-    if (rc < 0) break;
+    conn->sleeping.store(false, std::memory_order_seq_cst);
+    if (rc < 0) {
+      if (errno == EINTR) continue;
+      break;
+    }
     if (fds[1].revents & POLLIN) {
       uint64_t junk;
       while (read(conn->wake_fd, &junk, 8) > 0) {}
@@ -482,6 +691,7 @@ static void conn_loop(ClientConn* conn) {
       uint8_t buf[1 << 16];
       while (true) {
         ssize_t r = recv(conn->fd, buf, sizeof(buf), 0);
+        TransportStats::bump(conn->stats.recv_calls);
         if (r > 0) {
           ssize_t consumed = nghttp2_session_mem_recv(conn->sess, buf, r);
           if (consumed < 0) { conn->broken = true; break; }
@@ -680,30 +890,72 @@ class __attribute__((visibility("default"))) H2GrpcClient {
       call.deadline = deadline;
       call.slot = (int)i;
       if (rc[i].metadata) call.metadata = *rc[i].metadata;
-      call.payload = grpc_frame(
-          std::string((const char*)rc[i].payload, rc[i].payload_len));
+      // The call owns a copy of the wire (an early deadline return must not
+      // leave a connection thread reading the caller's staging memory), but
+      // it is the only copy: prefix and payload go straight into place.
+      grpc_frame_into(call.payload, rc[i].payload, rc[i].payload_len);
     }
+    submit_and_wait(batch, n, deadline);
+    return collect(*batch, n);
+  }
+
+  // counters summed over the client and its connections
+  std::unordered_map<std::string, uint64_t> stats() const {
+    std::unordered_map<std::string, uint64_t> m;
+    stats_.add_into(m);
+    for (auto& conn : conns_) conn->stats.add_into(m);
+    return m;
+  }
+
+ private:
+  // Queue the batch on the connections, wake the ones that sleep, wait for
+  // the last completion (or the hard deadline).  No GIL needed.
+  void submit_and_wait(const std::shared_ptr<Batch>& batch, size_t n,
+                       Clock::time_point deadline) {
+    batch->total = (int)n;
+    batch->stats = &stats_;
+    TransportStats::bump(stats_.batches);
+    TransportStats::bump(stats_.calls, n);
     size_t nc = conns_.size();
-    for (size_t i = 0; i < n; ++i) {
-      ClientConn* conn = conns_[i % nc].get();
-      std::lock_guard<std::mutex> lk(conn->mu);
-      conn->pending.push_back(QueuedCall{batch, &batch->calls[i]});
-    }
-    for (auto& conn : conns_) {
-      uint64_t one = 1;
-      (void)!write(conn->wake_fd, &one, 8);
-    }
-    {
-      std::unique_lock<std::mutex> lk(batch->mu);
-      auto hard = deadline + std::chrono::seconds(2);
-      while (batch->done.load() < (int)n) {
-        if (batch->cv.wait_until(lk, hard) == std::cv_status::timeout) break;
+    if (nc == 0 && n) throw std::runtime_error("client is closed");
+    size_t run = (size_t)transport_conn_run();
+    // Contiguous runs of `run` calls, dealt to the connections in turn; the
+    // first connection rotates per batch so concurrent batches start on
+    // different ones.  Each connection is locked and woken once per batch.
+    size_t start = next_conn_.fetch_add(1, std::memory_order_relaxed);
+    size_t nruns = (n + run - 1) / run;
+    size_t used = nruns < nc ? nruns : nc;
+    for (size_t j = 0; j < used; ++j) {
+      ClientConn* conn = conns_[(start + j) % nc].get();
+      {
+        std::lock_guard<std::mutex> lk(conn->mu);
+        for (size_t r = j; r < nruns; r += nc) {
+          size_t end = (r + 1) * run < n ? (r + 1) * run : n;
+          for (size_t i = r * run; i < end; ++i)
+            conn->pending.push_back(QueuedCall{batch, &batch->calls[i]});
+        }
+      }
+      // a thread that is not in poll picks `pending` up on its own
+      if (conn->sleeping.load(std::memory_order_seq_cst)) {
+        uint64_t one = 1;
+        (void)!write(conn->wake_fd, &one, 8);
+        TransportStats::bump(stats_.wake_writes);
       }
     }
+    std::unique_lock<std::mutex> lk(batch->mu);
+    // grace past the gRPC deadline so DEADLINE_EXCEEDED resolves cleanly
+    auto hard = deadline + std::chrono::seconds(2);
+    while (batch->done.load() < (int)n) {
+      if (batch->cv.wait_until(lk, hard) == std::cv_status::timeout) break;
+    }
+  }
+
+  static std::vector<std::tuple<int, std::string, std::string>> collect(
+      Batch& batch, size_t n) {
     std::vector<std::tuple<int, std::string, std::string>> out;
     out.reserve(n);
     for (size_t i = 0; i < n; ++i) {
-      Call& call = batch->calls[i];
+      Call& call = batch.calls[i];
       if (!call.done.load(std::memory_order_acquire)) {
         out.emplace_back(4, std::string(), "deadline exceeded");
         continue;
@@ -719,7 +971,6 @@ class __attribute__((visibility("default"))) H2GrpcClient {
     return out;
   }
 
- private:
   // submit the batch, wait for completion, return raw DATA byte streams
   std::vector<std::tuple<int, std::string, std::string>> invoke_collect(
       const std::vector<std::string>& paths, const std::vector<py::bytes>& payloads,
@@ -739,52 +990,24 @@ class __attribute__((visibility("default"))) H2GrpcClient {
       call.slot = (int)i;
       call.no_cap = no_cap;
       if (i < metadata.size()) call.metadata = metadata[i];
-      std::string raw = payloads[i];  // needs GIL; held here
-      call.payload = grpc_frame(raw);
+      // needs GIL; held here.  Copied once, straight behind the prefix.
+      char* data = nullptr;
+      Py_ssize_t len = 0;
+      if (PyBytes_AsStringAndSize(payloads[i].ptr(), &data, &len) != 0)
+        throw py::error_already_set();
+      grpc_frame_into(call.payload, data, (size_t)len);
     }
     {
       py::gil_scoped_release rel;
-      size_t nc = conns_.size();
-      for (size_t i = 0; i < n; ++i) {
-        ClientConn* conn = conns_[i % nc].get();
-        std::lock_guard<std::mutex> lk(conn->mu);
-        conn->pending.push_back(QueuedCall{batch, &batch->calls[i]});
-      }
-      for (auto& conn : conns_) {
-        uint64_t one = 1;
-        (void)!write(conn->wake_fd, &one, 8);
-      }
-      std::unique_lock<std::mutex> lk(batch->mu);
-      // grace past the gRPC deadline so DEADLINE_EXCEEDED resolves cleanly
-      auto hard = deadline + std::chrono::seconds(2);
-      while (batch->done.load() < (int)n) {
-        if (batch->cv.wait_until(lk, hard) == std::cv_status::timeout) break;
-      }
+      submit_and_wait(batch, n, deadline);
     }
-    std::vector<std::tuple<int, std::string, std::string>> out;
-    out.reserve(n);
-    for (size_t i = 0; i < n; ++i) {
-      Call& call = batch->calls[i];
-      if (!call.done.load(std::memory_order_acquire)) {
-        out.emplace_back(4, std::string(), "deadline exceeded");
-        continue;
-      }
-      if (call.overflow) {  // RESOURCE_EXHAUSTED, this slot only
-        out.emplace_back(8, std::string(),
-                         "response exceeds max_recv_msg_bytes");
-        continue;
-      }
-      out.emplace_back(call.grpc_status, std::move(call.response),
-                       call.grpc_message);
-    }
-    return out;
+    return collect(*batch, n);
   }
 
- public:
-
- private:
   std::string target_;
   std::vector<std::unique_ptr<ClientConn>> conns_;
+  TransportStats stats_;               // batches, calls, wakes, notifies
+  std::atomic<size_t> next_conn_{0};   // rotating first connection
 };
 
 // ---------------------------------------------------------------------------
@@ -805,7 +1028,7 @@ struct ServerConn {
   int fd = -1;
   nghttp2_session* sess = nullptr;
   std::unordered_map<int32_t, ServerStream> streams;
-  std::string wbuf;
+  WriteBuf wbuf;
   bool broken = false;
   class H2Server* server = nullptr;
 };
@@ -873,6 +1096,14 @@ class H2Server {
   // total requests handled (all routes) — lets tests assert exactly-once
   // invocation semantics of the gateway's fallback paths
   long request_count() const { return requests_.load(); }
+
+  // counters over all connections (calls = requests handled)
+  std::unordered_map<std::string, uint64_t> stats() const {
+    std::unordered_map<std::string, uint64_t> m;
+    stats_.add_into(m);
+    m["calls"] = (uint64_t)requests_.load(std::memory_order_relaxed);
+    return m;
+  }
 
   void handle(ServerStream& st) {
     requests_.fetch_add(1, std::memory_order_relaxed);
@@ -952,7 +1183,8 @@ class H2Server {
       }
       if (count < 1) count = 1;
       if (count > 65536) count = 65536;
-      std::string one = grpc_frame(std::string((const char*)msg, len));
+      std::string one;
+      grpc_frame_into(one, msg, len);
       st.response.reserve(one.size() * count);
       for (int64_t i = 0; i < count; ++i) st.response += one;
       return;
@@ -982,14 +1214,14 @@ class H2Server {
         st.response = grpc_frame(out);
         return;
       }
-      st.response = grpc_frame(make_hello_response(name));
+      hello_response_into(st.response, name);
     } else {
       if (!pb_validate(msg, len)) {
         st.grpc_status = 13;
         st.grpc_message = "malformed protobuf";
         return;
       }
-      st.response = grpc_frame(std::string((const char*)msg, len));
+      grpc_frame_into(st.response, msg, len);
     }
   }
 
@@ -1023,80 +1255,93 @@ class H2Server {
     st->sent += n;
     if (st->sent == st->response.size()) {
       *data_flags |= NGHTTP2_DATA_FLAG_EOF | NGHTTP2_DATA_FLAG_NO_END_STREAM;
-      std::string status = std::to_string(st->grpc_status);
-      std::vector<nghttp2_nv> trailers;
-      trailers.push_back(nv("grpc-status", status));
+      // a response with a body always has status 0 (respond()): constant
+      // trailers, nothing built per response
+      nghttp2_nv trailers[2] = {NV("grpc-status", "0", 11, 1), {}};
+      size_t nt = 1;
       if (!st->grpc_message.empty())
-        trailers.push_back(nv("grpc-message", st->grpc_message));
-      nghttp2_submit_trailer(sess, stream_id, trailers.data(), trailers.size());
+        trailers[nt++] = nv("grpc-message", st->grpc_message);
+      nghttp2_submit_trailer(sess, stream_id, trailers, nt);
     }
     return (ssize_t)n;
   }
 
   void respond(ServerConn* conn, int32_t sid, ServerStream& st) {
     handle(st);
-    std::string status = std::to_string(st.grpc_status);
     if (st.grpc_status != 0 || st.response.empty()) {
       // trailers-only response
-      std::vector<nghttp2_nv> hdrs;
-      hdrs.push_back(nv(":status", "200"));
-      hdrs.push_back(nv("content-type", "application/grpc"));
-      hdrs.push_back(nv("grpc-status", status));
+      char status[16];
+      int slen = snprintf(status, sizeof(status), "%d", st.grpc_status);
+      nghttp2_nv hdrs[4] = {
+          NV(":status", "200", 7, 3),
+          NV("content-type", "application/grpc", 12, 16),
+          NV("grpc-status", status, 11, slen),
+          {},
+      };
+      size_t nh = 3;
       if (!st.grpc_message.empty())
-        hdrs.push_back(nv("grpc-message", st.grpc_message));
-      nghttp2_submit_response(conn->sess, sid, hdrs.data(), hdrs.size(), nullptr);
+        hdrs[nh++] = nv("grpc-message", st.grpc_message);
+      nghttp2_submit_response(conn->sess, sid, hdrs, nh, nullptr);
       return;
     }
-    nghttp2_nv hdrs[] = {nv(":status", "200"), nv("content-type", "application/grpc")};
+    nghttp2_nv hdrs[] = {NV(":status", "200", 7, 3),
+                         NV("content-type", "application/grpc", 12, 16)};
     nghttp2_data_provider prd;
     prd.source.ptr = &st;
     prd.read_callback = resp_read;
     nghttp2_submit_response(conn->sess, sid, hdrs, 2, &prd);
   }
 
-  static int s_on_begin_headers(nghttp2_session*, const nghttp2_frame* frame, void* user) {
+  // The ServerStream (a node of `streams`: stable address) is the stream's
+  // user data, so the per-header / per-chunk callbacks need no map lookup.
+  // s_on_stream_close clears the user data before it erases the node: a
+  // server session may keep a closed stream in its map, and the pointer
+  // must not outlive the node.
+  static int s_on_begin_headers(nghttp2_session* sess, const nghttp2_frame* frame, void* user) {
     ServerConn* conn = (ServerConn*)user;
     if (frame->hd.type == NGHTTP2_HEADERS &&
         frame->headers.cat == NGHTTP2_HCAT_REQUEST)
-      conn->streams[frame->hd.stream_id];
+      nghttp2_session_set_stream_user_data(sess, frame->hd.stream_id,
+                                           &conn->streams[frame->hd.stream_id]);
     return 0;
   }
 
-  static int s_on_header(nghttp2_session*, const nghttp2_frame* frame,
+  static int s_on_header(nghttp2_session* sess, const nghttp2_frame* frame,
                          const uint8_t* name, size_t namelen, const uint8_t* value,
-                         size_t valuelen, uint8_t, void* user) {
-    ServerConn* conn = (ServerConn*)user;
-    auto it = conn->streams.find(frame->hd.stream_id);
-    if (it == conn->streams.end()) return 0;
-    if (namelen == 5 && memcmp(name, ":path", 5) == 0)
-      it->second.path.assign((const char*)value, valuelen);
+                         size_t valuelen, uint8_t, void*) {
+    ServerStream* st = (ServerStream*)nghttp2_session_get_stream_user_data(
+        sess, frame->hd.stream_id);
+    if (st && namelen == 5 && memcmp(name, ":path", 5) == 0)
+      st->path.assign((const char*)value, valuelen);
     return 0;
   }
 
-  static int s_on_data(nghttp2_session*, uint8_t, int32_t stream_id,
-                       const uint8_t* data, size_t len, void* user) {
-    ServerConn* conn = (ServerConn*)user;
-    auto it = conn->streams.find(stream_id);
-    if (it != conn->streams.end()) it->second.body.append((const char*)data, len);
+  static int s_on_data(nghttp2_session* sess, uint8_t, int32_t stream_id,
+                       const uint8_t* data, size_t len, void*) {
+    ServerStream* st =
+        (ServerStream*)nghttp2_session_get_stream_user_data(sess, stream_id);
+    if (st) st->body.append((const char*)data, len);
     return 0;
   }
 
-  static int s_on_frame_recv(nghttp2_session*, const nghttp2_frame* frame, void* user) {
+  static int s_on_frame_recv(nghttp2_session* sess, const nghttp2_frame* frame, void* user) {
     ServerConn* conn = (ServerConn*)user;
     if ((frame->hd.type == NGHTTP2_DATA || frame->hd.type == NGHTTP2_HEADERS) &&
         (frame->hd.flags & NGHTTP2_FLAG_END_STREAM)) {
-      auto it = conn->streams.find(frame->hd.stream_id);
-      if (it != conn->streams.end() && !it->second.responded) {
-        it->second.responded = true;
-        conn->server->respond(conn, frame->hd.stream_id, it->second);
+      ServerStream* st = (ServerStream*)nghttp2_session_get_stream_user_data(
+          sess, frame->hd.stream_id);
+      if (st && !st->responded) {
+        st->responded = true;
+        conn->server->respond(conn, frame->hd.stream_id, *st);
       }
     }
     return 0;
   }
 
-  static int s_on_stream_close(nghttp2_session*, int32_t stream_id, uint32_t,
+  static int s_on_stream_close(nghttp2_session* sess, int32_t stream_id, uint32_t,
                                void* user) {
     ServerConn* conn = (ServerConn*)user;
+    nghttp2_session_set_stream_user_data(sess, stream_id, nullptr);
     conn->streams.erase(stream_id);
     return 0;
   }
@@ -1124,7 +1369,7 @@ class H2Server {
 
     while (!stop_.load() && !conn.broken) {
       bool write_blocked = false;
-      if (!flush_session(conn.sess, conn.fd, conn.wbuf, &write_blocked))
+      if (!flush_session(conn.sess, conn.fd, conn.wbuf, &write_blocked, &stats_))
         conn.broken = true;
       if (conn.broken) break;
       pollfd pfd{conn.fd, (short)(POLLIN | (write_blocked ? POLLOUT : 0)), 0};
@@ -1134,6 +1379,7 @@ class H2Server {
         uint8_t buf[1 << 16];
         while (true) {
           ssize_t r = recv(conn.fd, buf, sizeof(buf), 0);
+          TransportStats::bump(stats_.recv_calls);
           if (r > 0) {
             if (nghttp2_session_mem_recv(conn.sess, buf, r) < 0) {
               conn.broken = true;
@@ -1164,5 +1410,6 @@ class H2Server {
   std::thread accept_thread_;
   std::atomic<bool> stop_{true};
   std::atomic<long> requests_{0};
+  TransportStats stats_;  // send/recv syscalls over all connections
 };
 

@@ -72,6 +72,9 @@ class ServiceDiscoverer:
         self._lock = threading.Lock()
         self._invocations = 0
         self._errors = 0
+        # print fields without presence even when zero/absent, so the JSON
+        # satisfies the advertised outputSchema (server.structured_content)
+        self.structured_content = bool(self.config.server.structured_content)
 
     # -- connection (discovery.go:65-89) -------------------------------------
 
@@ -237,6 +240,7 @@ class ServiceDiscoverer:
         return json_format.MessageToJson(
             msg, indent=None, ensure_ascii=False, preserving_proto_field_name=False,
             descriptor_pool=mi.output_descriptor.file.pool,
+            always_print_fields_with_no_presence=self.structured_content,
         )
 
     def invoke_wire(

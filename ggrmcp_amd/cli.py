@@ -56,6 +56,12 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
         help="HTTP surface: asyncio (full middleware parity) or the C++ "
              "batch reactor (production serving path)",
     )
+    ap.add_argument(
+        "--structured-content",
+        action="store_true",
+        help="return MCP structuredContent that satisfies each tool's "
+             "outputSchema (unpopulated fields printed)",
+    )
     return ap.parse_args(argv)
 
 
@@ -87,6 +93,8 @@ def build_config(args: argparse.Namespace) -> Config:
         cfg.gpu.devices = args.gpus
     if args.no_gpu:
         cfg.gpu.enabled = False
+    if getattr(args, "structured_content", False):
+        cfg.server.structured_content = True
     cfg.validate()
     return cfg
 

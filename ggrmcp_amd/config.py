@@ -133,6 +133,10 @@ class ServerConfig:
     # a single reactor measured ~25 us/request of parse+epoll+write
     reactors: int = 4
     security_headers_enabled: bool = True
+    # tools/call results also carry MCP structuredContent, printed with
+    # unpopulated no-presence fields so it satisfies the advertised
+    # outputSchema (the text block is the same JSON).  Off: today's bytes.
+    structured_content: bool = False
 
 
 @dataclass

@@ -49,6 +49,10 @@ E_UNSUPPORTED = 6
 E_OVERFLOW = 7
 E_NOT_TOOLCALL = 8
 
+# decode `mode` flag bits above the kind (mode & 3); mirror common.h DM_*
+DM_UNPOPULATED = 4
+DM_STRUCTURED = 8
+
 SR_ID_IS_MISSING = 1
 SR_SERVER_STREAMING = 2
 
@@ -183,6 +187,14 @@ class GpuEngine:
         # between them would silently mis-id responses), while the inner
         # batch ops also take the lock for standalone callers
         self._lock = threading.RLock()
+        self.structured_flags = 0
+        self.set_structured_content(self.config.server.structured_content)
+
+    def set_structured_content(self, on: bool) -> None:
+        """Serving spans print unpopulated fields and carry the object as
+        structuredContent too (sizes the final arena for both copies)."""
+        self._eng.set_structured_content(bool(on))
+        self.structured_flags = (DM_UNPOPULATED | DM_STRUCTURED) if on else 0
 
     # -- low-level batch ops -------------------------------------------------
 
@@ -250,6 +262,10 @@ class GpuEngine:
 class GpuPipeline:
     """Full tools/call pipeline over one GpuEngine + a ServiceDiscoverer."""
 
+    # host-assembled results carry structuredContent too
+    # (config.server.structured_content; set per instance in __init__)
+    structured_content = False
+
     def __init__(self, discoverer, config: Optional[Config] = None, device: int = 0,
                  invoke_workers: int = 64, wire_clients=None) -> None:
         self.discoverer = discoverer
@@ -267,6 +283,7 @@ class GpuPipeline:
         ]
         self.engine = self.engines[0]
         self.cpu = CpuTranscoder()
+        self.structured_content = bool(self.config.server.structured_content)
         # native C++ h2 transport per backend index (None -> grpcio threads)
         self.wire_clients = wire_clients
         self._invoke_pool = ThreadPoolExecutor(
@@ -401,7 +418,8 @@ class GpuPipeline:
                 rpc_error[i] = e
         st.invoke_ns += time.perf_counter_ns() - t0
 
-        dec, finals = engine.decode_batch(resp_wire, out_idx, mode=0)
+        dec, finals = engine.decode_batch(resp_wire, out_idx,
+                                          mode=0 | engine.structured_flags)
 
         # streaming: gather chunk lists, decode ALL chunks of ALL streams in
         # one value-mode GPU batch, assemble envelopes host-side
@@ -660,9 +678,11 @@ class GpuPipeline:
         UTF-8, over-cap, E_PARSE/E_LIMIT) — the RPC is NOT repeated."""
         mi = self._mi_by_idx[int(enc_r["tool_idx"])]
         try:
-            text = self.cpu.pb_to_json(mi.output_descriptor, wire)
+            on = self.structured_content
+            text = self.cpu.pb_to_json(mi.output_descriptor, wire, unpopulated=on)
             result = mcp.ToolCallResult(
-                content=[mcp.TextContent(text)], is_error=False
+                content=[mcp.TextContent(text)], is_error=False,
+                structured_content=json.loads(text) if on else None,
             )
             resp = mcp.JSONRPCResponse(id=rid, result=result.to_dict())
         except Exception as e:
@@ -678,7 +698,11 @@ class GpuPipeline:
             tool = params.get("name", "")
             args_json = json.dumps(params.get("arguments", {}), ensure_ascii=False)
             output = self.discoverer.invoke_method_by_tool(tool, args_json, hdr, timeout_s)
-            result = mcp.ToolCallResult(content=[mcp.TextContent(output)], is_error=False)
+            result = mcp.ToolCallResult(
+                content=[mcp.TextContent(output)], is_error=False,
+                structured_content=(
+                    json.loads(output) if self.structured_content else None),
+            )
             resp = mcp.JSONRPCResponse(id=rid, result=result.to_dict())
         except Exception as e:
             resp = mcp.JSONRPCResponse(
@@ -892,7 +916,9 @@ class BatchEngineInvoker:
             except Exception as e:
                 results[i] = e
         eng.stats.invoke_ns += time.perf_counter_ns() - t0
-        dec, jsons = eng.decode_batch(wires, out_idx, mode=1)
+        # bare JSON for the handler, which builds structuredContent from it
+        dec, jsons = eng.decode_batch(
+            wires, out_idx, mode=1 | (eng.structured_flags & DM_UNPOPULATED))
         for i in ok_slots:
             if wires[i] is None:
                 continue
@@ -903,7 +929,9 @@ class BatchEngineInvoker:
                 eng.stats.host_fallbacks += 1
                 mi = mis[i]
                 try:
-                    results[i] = pipeline.cpu.pb_to_json(mi.output_descriptor, wires[i])
+                    results[i] = pipeline.cpu.pb_to_json(
+                        mi.output_descriptor, wires[i],
+                        unpopulated=pipeline.structured_content)
                 except Exception as e:
                     results[i] = e
         return results

@@ -38,11 +38,15 @@ class CpuTranscoder:
         )
         return msg.SerializeToString()
 
-    def pb_to_json(self, desc: Descriptor, wire: bytes) -> str:
+    def pb_to_json(self, desc: Descriptor, wire: bytes,
+                   unpopulated: bool = False) -> str:
+        """``unpopulated`` also prints zero/empty fields without presence
+        (protojson EmitUnpopulated; the decode kernel's DM_UNPOPULATED)."""
         msg = self._cls(desc).FromString(wire)
         return json_format.MessageToJson(
             msg, indent=None, ensure_ascii=False, preserving_proto_field_name=False,
             descriptor_pool=desc.file.pool,
+            always_print_fields_with_no_presence=unpopulated,
         )
 
     def pb_to_message(self, desc: Descriptor, wire: bytes):

@@ -16,7 +16,7 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .batch import DECODE_DTYPE, E_OK, SLOT_DTYPE, _offsets
+from .batch import DECODE_DTYPE, DM_STRUCTURED, E_OK, SLOT_DTYPE, _offsets
 from .tables import compile_tables
 
 
@@ -80,7 +80,10 @@ class HostSimEngine:
         lens = [len(p) for p in safe]
         resp_off = _offsets(lens)
         scratch_off = _offsets([n * 8 + 1024 for n in lens], align=16)
-        final_off = _offsets([n * 16 + 2048 for n in lens], align=16)
+        # a structured envelope holds the JSON twice: escaped and raw
+        extra = [n * 8 + 1024 if mode & DM_STRUCTURED else 0 for n in lens]
+        final_off = _offsets([n * 16 + 2048 + x for n, x in zip(lens, extra)],
+                             align=16)
         raw, fin = self._eng.decode(
             data, resp_off, scratch_off, final_off,
             np.asarray(msg_indices, dtype=np.int32),

@@ -144,12 +144,16 @@ class Tool:
 class ToolCallResult:
     content: List[ContentBlock] = field(default_factory=list)
     is_error: bool = False
+    # MCP structuredContent: the result object the tool's outputSchema
+    # describes.  Emitted between content and isError, only when set.
+    structured_content: Optional[Dict[str, Any]] = None
 
     def to_dict(self) -> Dict[str, Any]:
-        return {
-            "content": [c.to_dict() for c in self.content],
-            "isError": self.is_error,
-        }
+        d: Dict[str, Any] = {"content": [c.to_dict() for c in self.content]}
+        if self.structured_content is not None:
+            d["structuredContent"] = self.structured_content
+        d["isError"] = self.is_error
+        return d
 
 
 def initialization_result() -> Dict[str, Any]:

@@ -162,6 +162,19 @@ struct __attribute__((packed)) DecodeResult {
 };
 static_assert(sizeof(DecodeResult) == 16, "DecodeResult layout");
 
+// decode kernel `mode` argument: (mode & DM_KIND) is 0 = JSON-RPC result
+// envelope, 1 = bare JSON, 2 = streaming content item; the flag bits ride
+// above it (mirrored by engine/batch.py DM_*).
+enum : int {
+  DM_KIND = 3,
+  // print singular no-presence fields that are zero or absent, and empty
+  // repeated/map fields (protojson EmitUnpopulated)
+  DM_UNPOPULATED = 4,
+  // envelope (kind 0) also carries the raw JSON as "structuredContent";
+  // needs final_cap + scratch_cap bytes of final arena per slot
+  DM_STRUCTURED = 8,
+};
+
 // protojson value ranges of the time WKTs (both directions refuse the rest)
 constexpr int64_t TS_MIN_SECONDS = -62135596800ll;  // 0001-01-01T00:00:00Z
 constexpr int64_t TS_MAX_SECONDS = 253402300799ll;  // 9999-12-31T23:59:59Z

@@ -153,6 +153,13 @@ inline size_t scratch_cap(size_t wire_len) {
 inline size_t final_cap(size_t wire_len) {
   return (wire_len * 16 + 2048 + 15) & ~(size_t)15;
 }
+// a DM_STRUCTURED envelope carries the JSON twice — escaped in the text
+// block and raw as structuredContent — so it also needs room for everything
+// the scratch arena can hold.  Without the flag the layout does not move.
+inline size_t final_cap(size_t wire_len, int mode) {
+  return final_cap(wire_len) +
+         ((mode & DM_STRUCTURED) ? scratch_cap(wire_len) : 0);
+}
 
 // JSON string escaping for C++-assembled error envelopes (error details may
 // contain quotes/control bytes)
@@ -573,7 +580,7 @@ class Engine : public spanapi::ISpanExecutor {
       throw std::runtime_error("input exceeds engine cap_in");
     if (scratch_bytes > d_scratch_.n) throw std::runtime_error("scratch cap");
     if (final_bytes > d_final_.n) throw std::runtime_error("final cap");
-    if (mode == 0 && n != last_batch_n_)
+    if ((mode & DM_KIND) == 0 && n != last_batch_n_)
       throw std::runtime_error("envelope decode batch must match last encode");
     std::memcpy(h_resp_.p, din.ptr, resp_bytes);
     uint32_t* h_off = (uint32_t*)h_off_.p;
@@ -596,7 +603,7 @@ class Engine : public spanapi::ISpanExecutor {
                         py::object skip, int mode) {
     int n = (int)py::len(items);
     if (n < 0 || n > max_batch_) throw std::runtime_error("bad batch size");
-    if (mode == 0 && n != last_batch_n_)
+    if ((mode & DM_KIND) == 0 && n != last_batch_n_)
       throw std::runtime_error("envelope decode batch must match last encode");
     uint32_t* resp_off = (uint32_t*)h_off_.p;
     uint32_t* final_off = resp_off + (n + 1);
@@ -627,7 +634,7 @@ class Engine : public spanapi::ISpanExecutor {
       if (len) std::memcpy(dst + acc, ptr, len);
       acc += len;
       sacc += scratch_cap(len);
-      facc += final_cap(len);
+      facc += final_cap(len, mode);
       if (has_skip) h_aux[n + i] = skipped ? 1 : 0;
     }
     resp_off[n] = (uint32_t)acc;
@@ -833,14 +840,14 @@ class Engine : public spanapi::ISpanExecutor {
         std::memcpy(rdst + racc, resp_ptr[i]->data() + rs[i].err_pos, len);
       racc += len;
       sacc += scratch_cap(len);
-      facc += final_cap(len);
+      facc += final_cap(len, span_flags_);
     }
     resp_off[n] = (uint32_t)racc;
     scratch_off[n] = (uint32_t)sacc;
     final_off[n] = (uint32_t)facc;
     if (sacc > d_scratch_.n) throw std::runtime_error("scratch cap");
     if (facc > d_final_.n) throw std::runtime_error("final cap");
-    py::tuple dec_out = run_decode(n, racc, facc, true, 0);
+    py::tuple dec_out = run_decode(n, racc, facc, true, 0 | span_flags_);
     last_dec_ms_ = std::chrono::duration<double, std::milli>(
                        std::chrono::steady_clock::now() - t_dec0)
                        .count();
@@ -1045,7 +1052,7 @@ class Engine : public spanapi::ISpanExecutor {
         // caller to either drop or re-invoke already-invoked slots
         if (resp_ptr[i] &&
             (racc + len > h_resp_.n || sacc + scratch_cap(len) > d_scratch_.n ||
-             facc + final_cap(len) > d_final_.n)) {
+             facc + final_cap(len, span_flags_) > d_final_.n)) {
           SlotOut& so = out->slots[i];
           so.kind = K_PY_DEC_FALLBACK;
           so.aux.assign(resp_ptr[i]->data() + rs[i].err_pos, len);
@@ -1062,7 +1069,7 @@ class Engine : public spanapi::ISpanExecutor {
         h_aux[n + i] = resp_ptr[i] ? 0 : 1;  // skip slots with no response
         racc += len;
         sacc += scratch_cap(len);
-        facc += final_cap(len);
+        facc += final_cap(len, span_flags_);
       }
       resp_off[n] = (uint32_t)racc;
       scratch_off[n] = (uint32_t)sacc;
@@ -1073,7 +1080,7 @@ class Engine : public spanapi::ISpanExecutor {
           std::memcpy(rdst + resp_off[i], resp_ptr[i]->data() + rs[i].err_pos,
                       len);
       });
-      run_decode_device(n, racc, facc, true, 0);
+      run_decode_device(n, racc, facc, true, 0 | span_flags_);
       auto t3 = std::chrono::steady_clock::now();
       out->dec_ms =
           std::chrono::duration<double, std::milli>(t3 - t2).count();
@@ -1106,6 +1113,13 @@ class Engine : public spanapi::ISpanExecutor {
       *err = e.what();
       return false;
     }
+  }
+
+  // Serving spans (run_span / process_span) print unpopulated fields and
+  // add structuredContent to every result envelope; their final arena is
+  // then sized for both copies of the JSON.  Off by default.
+  void set_structured_content(bool on) {
+    span_flags_ = on ? (DM_UNPOPULATED | DM_STRUCTURED) : 0;
   }
 
   // (encode_ms, invoke_ms, decode_ms) of the LAST process_span call;
@@ -1356,7 +1370,10 @@ class Engine : public spanapi::ISpanExecutor {
     int32_t* h_aux = (int32_t*)h_aux_.p;
     // route big mode-0 responses to the workgroup-cooperative kernel
     // (skip tag 2): the classic kernel skips them, k_pb2json_wg decodes
-    // one request per workgroup (common.h WG_DEC_*)
+    // one request per workgroup (common.h WG_DEC_*).  It knows neither DM_
+    // flag, hence `mode == 0` and not `kind == 0`: with a flag set, large
+    // responses stay on the classic kernel (correct, slower)
+    const int kind = mode & DM_KIND;
     int n_wg = 0;
     if (mode == 0 && has_skip) {
       uint32_t thr = wg_dec_min();
@@ -1377,7 +1394,7 @@ class Engine : public spanapi::ISpanExecutor {
     // stream2_ overlap the per-chunk kernels on stream_ (see
     // run_encode_chunked; the compact/D2H tail below is shared)
     bool chunked = false;
-    if (mode == 0 && has_skip && n >= 2 && pipe_chunks() > 1 &&
+    if (kind == 0 && has_skip && n >= 2 && pipe_chunks() > 1 &&
         resp_bytes >= pipe_min_bytes()) {
       int cut[PIPE_MAX_CHUNKS + 1];
       int C = pipe_cuts(h_off, n, pipe_chunks(), cut);
@@ -1402,7 +1419,7 @@ class Engine : public spanapi::ISpanExecutor {
                 (const uint32_t*)d_off + 2 * (n + 1) + lo,
                 (uint8_t*)d_final_.p, (const uint32_t*)d_off + (n + 1) + lo,
                 (DecodeResult*)d_dec_results_.p + lo,
-                (const int32_t*)d_aux + n + lo, tables_, m, 0);
+                (const int32_t*)d_aux + n + lo, tables_, m, mode);
             HIP_CHECK(hipGetLastError());
           }
           if (n_wg > 0) {
@@ -1433,7 +1450,7 @@ class Engine : public spanapi::ISpanExecutor {
           k_pb2json, dim3(blocks), dim3(WPB * WAVE), 0, stream_,
           (const uint8_t*)d_resp_.p, (const uint32_t*)d_off,
           (const int32_t*)d_aux, (const uint8_t*)d_id_slots_.p,
-          mode == 0 ? (const SlotResult*)d_results_.p : nullptr,
+          kind == 0 ? (const SlotResult*)d_results_.p : nullptr,
           (uint8_t*)d_scratch_.p, (const uint32_t*)d_off + 2 * (n + 1),
           (uint8_t*)d_final_.p, (const uint32_t*)d_off + (n + 1),
           (DecodeResult*)d_dec_results_.p,
@@ -1526,6 +1543,7 @@ class Engine : public spanapi::ISpanExecutor {
   double last_enc_ms_ = 0.0, last_inv_ms_ = 0.0, last_dec_ms_ = 0.0;
   double last_enc_gpu_ms_ = 0.0, last_dec_gpu_ms_ = 0.0;
   int last_batch_n_ = -1;
+  int span_flags_ = 0;  // DM_* flags OR-ed into the serving spans' decode mode
   bool compact_used_ = false;
   size_t compact_bytes_ = 0;
   size_t last_final_bytes_ = 0;
@@ -1645,6 +1663,8 @@ PYBIND11_MODULE(_jsonproto, m) {
            py::arg("enforce") = 1)
       .def("decode_list", &Engine::decode_list, py::arg("items"),
            py::arg("msg_idx"), py::arg("skip") = py::none(), py::arg("mode") = 0)
+      .def("set_structured_content", &Engine::set_structured_content,
+           py::arg("on"))
       .def("last_stage_ms", &Engine::last_stage_ms)
       .def("last_gpu_ms", &Engine::last_gpu_ms)
       .def("span_handle",

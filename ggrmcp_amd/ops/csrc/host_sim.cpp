@@ -99,8 +99,9 @@ class HostEngine {
       skip_ptr = skip_arr.data();
     }
     run_pb2json((const uint8_t*)din.ptr, resp_off.data(), msg_idx.data(),
-                mode == 0 ? last_ids_.data() : nullptr,
-                mode == 0 ? last_results_.data() : nullptr, scratch.data(),
+                (mode & DM_KIND) == 0 ? last_ids_.data() : nullptr,
+                (mode & DM_KIND) == 0 ? last_results_.data() : nullptr,
+                scratch.data(),
                 scratch_off.data(), fin.data(), final_off.data(),
                 results.data(), skip_ptr, n, mode);
     py::array_t<uint8_t> res({(py::ssize_t)(n * sizeof(DecodeResult))});

@@ -9,6 +9,10 @@
 //   {"jsonrpc":"2.0","id":<id>,"result":{"content":[{"type":"text",
 //    "text":"<escaped>"}],"isError":false}}.
 //
+// With DM_STRUCTURED the same JSON follows once more, raw, as
+// "structuredContent"; with DM_UNPOPULATED the walker also prints zero and
+// absent fields without presence (docs/KERNELS.md, "Unpopulated fields").
+//
 // protojson output semantics: camelCase field names, 64-bit ints quoted,
 // enums by name (unknown values by number), bytes as padded std base64,
 // default-valued non-presence fields omitted, Timestamp/Duration RFC3339 /
@@ -47,6 +51,9 @@ struct DCtx {
   Tables t;
   int32_t status;
   int lane;
+  // walker option (DM_UNPOPULATED or 0).  Default-initialised so contexts
+  // that never set it (the workgroup kernel's) keep default omission.
+  uint32_t unpop = 0;
 };
 
 DEV bool dfail(DCtx& c, int32_t code) {
@@ -955,6 +962,49 @@ DEVN bool emit_map_default_value(DCtx& c, const FieldEntry& vf) {
   }
 }
 
+// DM_UNPOPULATED gap fill: print the default of every field of message
+// `msg_idx` numbered in the open interval (lo, hi) that has neither presence
+// nor a oneof — `"name":0`, `"name":""`, `"name":[]`, `"name":{}` — in
+// field-number order.  The walker refuses out-of-order wire, so the fields
+// a body did not carry are exactly the ones between the numbers it did;
+// the table is sorted by number, so no per-frame "seen" state is needed.
+// *first_member is the frame's comma state.  Out of line on purpose: the
+// walker's register budget must not pay for this cold loop.
+DEVN bool fill_unpopulated(DCtx& c, int32_t msg_idx, uint32_t lo, uint32_t hi,
+                           uint8_t* first_member) {
+  const MsgEntry& m = c.t.msgs[msg_idx];
+  int i;
+  if (lo < (uint32_t)m.field_count &&
+      c.t.fields[m.field_start + lo].number == lo + 1) {
+    i = (int)lo;  // densely numbered: position == number - 1
+  } else {
+    int a = 0, b = m.field_count;  // first field numbered above lo
+    while (a < b) {
+      int mid = (a + b) >> 1;
+      if (c.t.fields[m.field_start + mid].number <= lo) a = mid + 1;
+      else b = mid;
+    }
+    i = a;
+  }
+  for (; i < m.field_count; ++i) {
+    const FieldEntry& fe = c.t.fields[m.field_start + i];
+    if (fe.number >= hi) break;
+    if (fe.flags & (F_HAS_PRESENCE | F_ONEOF)) continue;
+    if (!*first_member && !putc_(c, ',')) return false;
+    *first_member = 0;
+    if (!putc_(c, '"')) return false;
+    if (!puts_(c, (const char*)(c.t.names + fe.json_off), fe.json_len))
+      return false;
+    if (!puts_(c, "\":", 2)) return false;
+    bool ok;
+    if (fe.flags & F_MAP) ok = puts_(c, "{}", 2);
+    else if (fe.flags & F_REPEATED) ok = puts_(c, "[]", 2);
+    else ok = emit_map_default_value(c, fe);
+    if (!ok) return false;
+  }
+  return true;
+}
+
 // ---- scalar WKT leaves (no nesting) ----------------------------------------
 
 DEVN bool decode_ts_dur_body(DCtx& c, uint32_t end, bool is_ts) {
@@ -1292,7 +1342,17 @@ DEVN bool map_entry_step(DCtx& c, DFrame& f, uint32_t eend, DFrame* stack,
   }
   if (!emit_map_key(c, kf, key_pos, have_key)) return false;
   if (!have_val) {
-    if (!emit_map_default_value(c, vf)) return false;
+    if (c.unpop && vf.kind == K_MESSAGE &&
+        c.t.msgs[vf.sub_index].wkt_kind == WKT_NONE) {
+      // an absent plain-message value prints that message's own defaults
+      uint8_t first = 1;
+      if (!putc_(c, '{')) return false;
+      if (!fill_unpopulated(c, vf.sub_index, 0, 0xFFFFFFFFu, &first))
+        return false;
+      if (!putc_(c, '}')) return false;
+    } else if (!emit_map_default_value(c, vf)) {
+      return false;
+    }
     c.pos = eend;
     return true;
   }
@@ -1568,6 +1628,9 @@ DEV bool decode_walk(DCtx& c, int top_msg_idx, uint32_t top_end,
       // a field that runs past its message (an Any payload cut short, say)
       // must not hand the parent a cursor inside its next field
       if (c.pos > f.end) return dfail(c, E_PARSE);
+      if (c.unpop && !fill_unpopulated(c, f.msg_idx, f.prev_number,
+                                       0xFFFFFFFFu, &f.first_member))
+        return false;
       if (!(bare_top && sp == 1) && !putc_(c, '}')) return false;
       --sp;
       continue;
@@ -1598,11 +1661,15 @@ DEV bool decode_walk(DCtx& c, int top_msg_idx, uint32_t top_end,
     }
     // out-of-order / non-adjacent duplicates -> host transcodes
     if (num <= f.prev_number) return dfail(c, E_UNSUPPORTED);
+    if (c.unpop &&
+        !fill_unpopulated(c, f.msg_idx, f.prev_number, num, &f.first_member))
+      return false;
     f.prev_number = num;
     bool repeated = (fe->flags & F_REPEATED) != 0;
     bool is_map = (fe->flags & F_MAP) != 0;
-    // proto3 default-omission for singular non-presence fields
-    if (!repeated && !(fe->flags & F_HAS_PRESENCE)) {
+    // proto3 default-omission for singular non-presence fields (an explicit
+    // zero prints under DM_UNPOPULATED, like an absent one)
+    if (!repeated && !(fe->flags & F_HAS_PRESENCE) && !c.unpop) {
       if (wt == W_VARINT) {
         uint32_t save = c.pos;
         uint64_t v;
@@ -1749,6 +1816,7 @@ extern "C" __global__ void __launch_bounds__(WPB * WAVE) k_pb2json(
     Tables t, int n_req, int mode) {
   int wave_in_block = threadIdx.x / WAVE;
   int lane = lane_id();
+  const int kind = mode & DM_KIND;
   for (int req = blockIdx.x * WPB + wave_in_block; req < n_req;
        req += gridDim.x * WPB) {
     DecodeResult r;
@@ -1772,6 +1840,9 @@ extern "C" __global__ void __launch_bounds__(WPB * WAVE) k_pb2json(
     c.t = t;
     c.status = E_OK;
     c.lane = lane;
+    // a stream of messages is not one object of the output schema: the
+    // streaming item (kind 2) ignores both flags
+    c.unpop = kind != 2 ? (uint32_t)(mode & DM_UNPOPULATED) : 0u;
     decode_walk(c, msg_idx_arr[req], c.len);
     if (c.status != E_OK) {
       r.status = c.status;
@@ -1791,7 +1862,7 @@ extern "C" __global__ void __launch_bounds__(WPB * WAVE) k_pb2json(
     o.t = t;
     o.status = E_OK;
     o.lane = lane;
-    if (mode == 1) {
+    if (kind == 1) {
       // bare JSON (transcode tests): copy scratch out
       if (json_len > o.ocap) {
         r.status = E_OVERFLOW;
@@ -1801,7 +1872,7 @@ extern "C" __global__ void __launch_bounds__(WPB * WAVE) k_pb2json(
       for (uint32_t i = lane; i < json_len; i += WAVE)
         o.out[i] = scratch[scratch_off[req] + i];
       o.opos = json_len;
-    } else if (mode == 2) {
+    } else if (kind == 2) {
       // streaming content item: the chunk pre-wrapped + escaped so the host
       // assembles a multi-chunk ToolCallResult by joining byte slices
       // (json-escaping 4096 chunk texts per stream in Python dominated the
@@ -1836,7 +1907,22 @@ extern "C" __global__ void __launch_bounds__(WPB * WAVE) k_pb2json(
       }
       if (ok) ok = puts_(o, P2, sizeof(P2) - 1);
       if (ok) ok = put_escaped(o, scratch + scratch_off[req], json_len);
-      if (ok) ok = puts_(o, P3, sizeof(P3) - 1);
+      if (ok && (mode & DM_STRUCTURED)) {
+        // the same object once more, raw: MCP structuredContent.  The text
+        // block above is its serialization, byte for byte.
+        static const char S1[] = "\"}],\"structuredContent\":";
+        static const char S2[] = ",\"isError\":false}}";
+        ok = puts_(o, S1, sizeof(S1) - 1);
+        if (ok && o.opos + json_len > o.ocap) ok = dfail(o, E_OVERFLOW);
+        if (ok) {
+          for (uint32_t i = lane; i < json_len; i += WAVE)
+            o.out[o.opos + i] = scratch[scratch_off[req] + i];
+          o.opos += json_len;
+          ok = puts_(o, S2, sizeof(S2) - 1);
+        }
+      } else if (ok) {
+        ok = puts_(o, P3, sizeof(P3) - 1);
+      }
       if (!ok) {
         r.status = o.status;
         if (!lane) results[req] = r;

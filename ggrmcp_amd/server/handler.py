@@ -109,6 +109,10 @@ class MCPHandler:
         )
         self.validator = Validator()
         self.invoker = invoker or CPUInvoker(discoverer)
+        # unary successes also carry the object as MCP structuredContent;
+        # the invoker's JSON then has unpopulated fields printed, so it
+        # satisfies the tool's outputSchema
+        self.structured_content = bool(self.config.server.structured_content)
         self.start_time = time.time()
 
     # -- top-level routing ----------------------------------------------------
@@ -235,10 +239,14 @@ class MCPHandler:
                     tool_name, args_json, headers, timeout_s
                 )
                 content = [mcp.TextContent(c) for c in chunks]
+                structured = None  # a stream is not one object of the schema
             else:
                 output = await self.invoker.invoke(tool_name, args_json, headers, timeout_s)
                 content = [mcp.TextContent(output)]
-            result = mcp.ToolCallResult(content=content, is_error=False)
+                structured = json.loads(output) if self.structured_content else None
+            result = mcp.ToolCallResult(
+                content=content, is_error=False, structured_content=structured
+            )
         except grpc.RpcError as e:
             # gRPC errors -> isError result, HTTP 200 (handler.go:252-259)
             code = e.code().name if hasattr(e, "code") else "UNKNOWN"

@@ -85,8 +85,10 @@ class CpuBatchPipeline:
                 else:
                     out = self.discoverer.invoke_method_by_tool(
                         params.get("name", ""), args_json, hdr, timeout_s)
+                    on = getattr(self.discoverer, "structured_content", False)
                     result = mcp.ToolCallResult(
-                        content=[mcp.TextContent(out)], is_error=False)
+                        content=[mcp.TextContent(out)], is_error=False,
+                        structured_content=json.loads(out) if on else None)
                 resp = mcp.JSONRPCResponse(id=rid, result=result.to_dict())
             except KeyError:
                 resp = mcp.JSONRPCResponse(

@@ -34,8 +34,10 @@
 #include "json2pb.hip"
 #include "pb2json.hip"
 #include "span_api.h"
+#include "span_host.h"
 
 namespace py = pybind11;
+using namespace spanhost;
 
 #define HIP_CHECK(expr)                                                     \
   do {                                                                      \
@@ -161,55 +163,6 @@ inline size_t final_cap(size_t wire_len, int mode) {
          ((mode & DM_STRUCTURED) ? scratch_cap(wire_len) : 0);
 }
 
-// JSON string escaping for C++-assembled error envelopes (error details may
-// contain quotes/control bytes)
-void json_escape_append(std::string& out, const char* s, size_t n) {
-  static const char* hex = "0123456789abcdef";
-  for (size_t i = 0; i < n; ++i) {
-    unsigned char c = (unsigned char)s[i];
-    if (c == '"' || c == '\\') {
-      out.push_back('\\');
-      out.push_back((char)c);
-    } else if (c == '\n') {
-      out += "\\n";
-    } else if (c == '\r') {
-      out += "\\r";
-    } else if (c == '\t') {
-      out += "\\t";
-    } else if (c < 0x20) {
-      out += "\\u00";
-      out.push_back(hex[c >> 4]);
-      out.push_back(hex[c & 15]);
-    } else {
-      out.push_back((char)c);
-    }
-  }
-}
-
-// grpc status code -> canonical name (mirrors backend/native_invoker.py
-// _CODE_NAMES so native and Python error texts match)
-const char* grpc_status_name(int s) {
-  static const char* names[] = {
-      "OK", "CANCELLED", "UNKNOWN", "INVALID_ARGUMENT", "DEADLINE_EXCEEDED",
-      "NOT_FOUND", "ALREADY_EXISTS", "PERMISSION_DENIED", "RESOURCE_EXHAUSTED",
-      "FAILED_PRECONDITION", "ABORTED", "OUT_OF_RANGE", "UNIMPLEMENTED",
-      "INTERNAL", "UNAVAILABLE", "DATA_LOSS", "UNAUTHENTICATED"};
-  return (s >= 0 && s < 17) ? names[s] : "CODE_?";
-}
-
-// kernel status -> JSON-RPC (code, message); mirrors engine/batch.py
-// _STATUS_TO_RPC (reference error mapping handler.go:117-127)
-void status_to_rpc(int status, int* code, const char** msg) {
-  switch (status) {
-    case E_PARSE: *code = -32700; *msg = "parse error"; break;
-    case E_INVALID_REQUEST: *code = -32600; *msg = "invalid request"; break;
-    case E_METHOD_NOT_FOUND: *code = -32601; *msg = "tool not found"; break;
-    case E_INVALID_PARAMS: *code = -32602; *msg = "invalid params"; break;
-    case E_LIMIT: *code = -32602; *msg = "argument limits exceeded"; break;
-    default: *code = -32603; *msg = "internal error"; break;
-  }
-}
-
 }  // namespace
 
 // Parallel staging: the span executor's per-batch memcpys into pinned
@@ -305,6 +258,18 @@ inline size_t stage_min_bytes() {
   const char* e = getenv("GGRMCP_STAGE_MIN");
   return e ? (size_t)atoll(e) : (size_t)(1u << 20);
 }
+
+using SlotMeta = std::vector<std::pair<std::string, std::string>>;
+using CallsPerBackend = std::vector<std::vector<H2GrpcClient::RawCall>>;
+// a delivered unary response payload (p == nullptr: none) and the arena
+// bytes Engine::stage_responses laid out
+struct Payload {
+  const char* p = nullptr;
+  size_t len = 0;
+};
+struct Staged {
+  size_t resp, scratch, fin;
+};
 
 class Engine : public spanapi::ISpanExecutor {
  public:
@@ -652,8 +617,10 @@ class Engine : public spanapi::ISpanExecutor {
   // into the decode staging, all under one GIL hold with releases around
   // the GPU and network waits.  Streaming / error slots are reported back
   // for the Python host paths.  Returns:
-  //   (enc_results, dec_results, out_view, pb_view, rpc_errors)
-  // rpc_errors: list of None | (grpc_status, message) per slot.
+  //   (enc_results, dec_results, out_view, stream_pbs, rpc_errors, resp_wires)
+  // stream_pbs: None | request wire of a streaming slot;
+  // rpc_errors: None | (grpc_status, message);
+  // resp_wires: None | delivered response wire the GPU decode rejected.
   py::tuple process_span(py::sequence bodies, py::object headers,
                          py::object clients_obj, double timeout_s,
                          uint32_t max_depth, uint32_t max_string,
@@ -668,31 +635,16 @@ class Engine : public spanapi::ISpanExecutor {
     // stage + encode (run_encode manages its own GIL release)
     int n = (int)py::len(bodies);
     if (n < 0 || n > max_batch_) throw std::runtime_error("bad batch size");
-    uint32_t* in_off = (uint32_t*)h_off_.p;
-    uint32_t* pb_off = in_off + (n + 1);
-    size_t acc = 0, pacc = 0;
-    uint8_t* dst = (uint8_t*)h_in_.p;
     std::vector<const char*> bptr(n);
-    for (int i = 0; i < n; ++i) {
-      size_t len;
-      if (!view_of(bodies[i], &bptr[i], &len))
+    std::vector<size_t> blen(n);
+    for (int i = 0; i < n; ++i)
+      if (!view_of(bodies[i], &bptr[i], &blen[i]))
         throw std::runtime_error("process_span: unsupported element type");
-      if (acc + len > h_in_.n) throw std::runtime_error("input exceeds cap_in");
-      in_off[i] = (uint32_t)acc;
-      pb_off[i] = (uint32_t)pacc;
-      acc += len;
-      pacc += pb_cap(len);
-    }
-    in_off[n] = (uint32_t)acc;
-    pb_off[n] = (uint32_t)pacc;
-    if (pacc > d_pb_.n) throw std::runtime_error("pb cap exceeded");
-    // copies fan out across the staging pool for big batches (the byte
-    // buffers stay alive via the borrowed sequence refs; the caller
-    // keeps the GIL while the helpers copy)
-    stage_copies(in_off, n, acc, [&](int i) {
-      size_t len = in_off[i + 1] - in_off[i];
-      if (len) std::memcpy(dst + in_off[i], bptr[i], len);
-    });
+    // (the byte buffers stay alive via the borrowed sequence refs; the
+    // caller keeps the GIL while the staging helpers copy)
+    size_t acc = 0, pacc = 0;
+    if (const char* why = stage_bodies(bptr.data(), blen.data(), n, &acc, &pacc))
+      throw std::runtime_error(why);
     // per-slot metadata (headers) staged before dropping the GIL
     std::vector<std::vector<std::pair<std::string, std::string>>> metas;
     bool have_headers = !headers.is_none();
@@ -720,30 +672,20 @@ class Engine : public spanapi::ISpanExecutor {
     // route OK unary slots per backend
     SlotResult* rs = (SlotResult*)h_results_.p;
     size_t nb = clients.size();
-    std::vector<std::vector<H2GrpcClient::RawCall>> per_be(nb);
+    CallsPerBackend per_be(nb);
     std::vector<std::vector<int>> slots_be(nb);
-    uint8_t* pb = (uint8_t*)h_pb_.p;
-    for (int i = 0; i < n; ++i) {
-      if (rs[i].status != E_OK || (rs[i].flags & SR_SERVER_STREAMING)) continue;
-      int tool = rs[i].tool_idx;
-      if (tool < 0 || tool >= (int)tool_paths_.size()) continue;
-      size_t be = tool < (int)tool_backend_.size()
-                      ? (size_t)tool_backend_[tool] % nb
-                      : 0;
-      const std::string& path = tool_paths_[tool];
-      per_be[be].push_back(H2GrpcClient::RawCall{
-          path.data(), path.size(), pb + rs[i].pb_off, rs[i].pb_len,
-          have_headers && !metas[i].empty() ? &metas[i] : nullptr});
-      slots_be[be].push_back(i);
-    }
+    for (int i = 0; i < n; ++i)
+      if (rs[i].status == E_OK && !(rs[i].flags & SR_SERVER_STREAMING))
+        route_unary(i, have_headers ? &metas[i] : nullptr, per_be, slots_be);
 
     // streaming slots: copy their request wire OUT now — run_decode's
     // output compaction reuses h_pb_, which would clobber them before the
     // Python streaming fan-out reads the bytes
     py::list stream_pbs(n);
+    const char* pb = (const char*)h_pb_.p;
     for (int i = 0; i < n; ++i) {
       if (rs[i].status == E_OK && (rs[i].flags & SR_SERVER_STREAMING))
-        stream_pbs[i] = py::bytes((const char*)pb + rs[i].pb_off, rs[i].pb_len);
+        stream_pbs[i] = py::bytes(pb + rs[i].pb_off, rs[i].pb_len);
       else
         stream_pbs[i] = py::none();
     }
@@ -765,89 +707,28 @@ class Engine : public spanapi::ISpanExecutor {
     last_inv_ms_ =
         std::chrono::duration<double, std::milli>(t_dec0 - t_inv0).count();
 
-    // stage responses for decode
-    uint32_t* resp_off = (uint32_t*)h_off_.p;
-    uint32_t* final_off = resp_off + (n + 1);
-    uint32_t* scratch_off = resp_off + 2 * (n + 1);
-    int32_t* h_aux = (int32_t*)h_aux_.p;
-    std::vector<const std::string*> resp_ptr(n, nullptr);
+    // parse the replies, then stage the delivered payloads for decode
+    std::vector<Payload> resp(n);
     py::list rpc_errors(n);
     for (int i = 0; i < n; ++i) rpc_errors[i] = py::none();
     for (size_t b = 0; b < nb; ++b) {
       for (size_t k = 0; k < slots_be[b].size(); ++k) {
         int i = slots_be[b][k];
         auto& r = res_be[b][k];
-        int status = std::get<0>(r);
-        const std::string& data = std::get<1>(r);
-        size_t plen = 0, poff = 0;
-        bool compressed = false, truncated = false;
-        if (!data.empty()) {
-          if (data.size() >= 5) {
-            // gRPC frame: [compressed-flag u8][len u32be][payload]
-            compressed = data[0] != 0;
-            uint32_t len;
-            memcpy(&len, data.data() + 1, 4);
-            len = ntohl(len);
-            if (data.size() >= 5 + (size_t)len) {
-              poff = 5;
-              plen = len;
-            } else {
-              truncated = true;
-            }
-          } else {
-            truncated = true;
-          }
-        }
-        // A stream that closed without a decodable grpc-status trailer is
-        // malformed (gRPC requires trailers) — never treat it as OK, even
-        // when DATA arrived (engine.cpp:489).
-        if (status < 0) {
-          std::string msg = std::get<2>(r);
-          if (msg.empty()) msg = "stream closed without grpc-status";
-          rpc_errors[i] = py::make_tuple(2 /*UNKNOWN*/, py::str(msg));
-        } else if (status == 0 && compressed) {
-          rpc_errors[i] = py::make_tuple(
-              13 /*INTERNAL*/,
-              py::str("compressed gRPC response frame not supported"));
-        } else if (status == 0 && truncated) {
-          rpc_errors[i] =
-              py::make_tuple(13 /*INTERNAL*/, py::str("truncated gRPC frame"));
-        } else if (status == 0) {
-          resp_ptr[i] = &std::get<1>(res_be[b][k]);
-          // record the unary payload span via aux arrays below
-          rs[i].err_pos = (uint32_t)poff;   // reuse: payload offset
-          rs[i].aux = (int32_t)plen;        // reuse: payload length
-        } else {
-          rpc_errors[i] = py::make_tuple(status, py::str(std::get<2>(r)));
-        }
+        GrpcReply g =
+            parse_grpc_reply(std::get<0>(r), std::get<1>(r), std::get<2>(r));
+        if (g.status == 0)
+          resp[i] = {std::get<1>(r).data() + g.off, g.len};
+        else
+          rpc_errors[i] = py::make_tuple(g.status, py::str(g.err));
       }
     }
-    size_t racc = 0, sacc = 0, facc = 0;
-    uint8_t* rdst = (uint8_t*)h_resp_.p;
-    for (int i = 0; i < n; ++i) {
-      size_t len = 0;
-      if (resp_ptr[i]) len = (size_t)rs[i].aux;
-      if (racc + len > h_resp_.n) throw std::runtime_error("resp cap");
-      resp_off[i] = (uint32_t)racc;
-      scratch_off[i] = (uint32_t)sacc;
-      final_off[i] = (uint32_t)facc;
-      h_aux[i] = (rs[i].status == E_OK && !(rs[i].flags & SR_SERVER_STREAMING) &&
-                  tool_out_msg_.size() > (size_t)rs[i].tool_idx)
-                     ? tool_out_msg_[rs[i].tool_idx]
-                     : 0;
-      h_aux[n + i] = resp_ptr[i] ? 0 : 1;  // skip slots with no response
-      if (len)
-        std::memcpy(rdst + racc, resp_ptr[i]->data() + rs[i].err_pos, len);
-      racc += len;
-      sacc += scratch_cap(len);
-      facc += final_cap(len, span_flags_);
-    }
-    resp_off[n] = (uint32_t)racc;
-    scratch_off[n] = (uint32_t)sacc;
-    final_off[n] = (uint32_t)facc;
-    if (sacc > d_scratch_.n) throw std::runtime_error("scratch cap");
-    if (facc > d_final_.n) throw std::runtime_error("final cap");
-    py::tuple dec_out = run_decode(n, racc, facc, true, 0 | span_flags_);
+    // an arena overflow fails the whole span here
+    Staged st = stage_responses(
+        n, resp, [](int, const char* what) { throw std::runtime_error(what); });
+    if (st.scratch > d_scratch_.n) throw std::runtime_error("scratch cap");
+    if (st.fin > d_final_.n) throw std::runtime_error("final cap");
+    py::tuple dec_out = run_decode(n, st.resp, st.fin, true, 0 | span_flags_);
     last_dec_ms_ = std::chrono::duration<double, std::milli>(
                        std::chrono::steady_clock::now() - t_dec0)
                        .count();
@@ -859,9 +740,8 @@ class Engine : public spanapi::ISpanExecutor {
     DecodeResult* dr = (DecodeResult*)h_dec_results_.p;
     py::list resp_wires(n);
     for (int i = 0; i < n; ++i) {
-      if (resp_ptr[i] && (dr[i].status != E_OK || dr[i].out_len == 0))
-        resp_wires[i] = py::bytes(resp_ptr[i]->data() + rs[i].err_pos,
-                                  (size_t)rs[i].aux);
+      if (resp[i].p && (dr[i].status != E_OK || dr[i].out_len == 0))
+        resp_wires[i] = py::bytes(resp[i].p, resp[i].len);
       else
         resp_wires[i] = py::none();
     }
@@ -887,31 +767,10 @@ class Engine : public spanapi::ISpanExecutor {
         return false;
       }
       out->slots.assign(n, SlotOut());
-      // stage bodies into pinned memory (offsets serial, copies fanned
-      // out across the staging pool for big batches)
-      uint32_t* in_off = (uint32_t*)h_off_.p;
-      uint32_t* pb_off = in_off + (n + 1);
       size_t acc = 0, pacc = 0;
-      uint8_t* dst = (uint8_t*)h_in_.p;
-      for (int i = 0; i < n; ++i) {
-        size_t len = in.body_lens[i];
-        if (acc + len > h_in_.n) {
-          *err = "input exceeds cap_in";
-          return false;
-        }
-        in_off[i] = (uint32_t)acc;
-        pb_off[i] = (uint32_t)pacc;
-        acc += len;
-        pacc += pb_cap(len);
-      }
-      in_off[n] = (uint32_t)acc;
-      pb_off[n] = (uint32_t)pacc;
-      stage_copies(in_off, n, acc, [&](int i) {
-        size_t len = in_off[i + 1] - in_off[i];
-        if (len) std::memcpy(dst + in_off[i], in.bodies[i], len);
-      });
-      if (pacc > d_pb_.n) {
-        *err = "pb cap exceeded";
+      if (const char* why =
+              stage_bodies(in.bodies, in.body_lens, n, &acc, &pacc)) {
+        *err = why;
         return false;
       }
       Limits lim{in.max_depth, in.max_string, in.max_args,
@@ -924,11 +783,11 @@ class Engine : public spanapi::ISpanExecutor {
       out->enc_gpu_ms = last_enc_gpu_ms_;
 
       SlotResult* rs = (SlotResult*)h_results_.p;
-      uint8_t* pb = (uint8_t*)h_pb_.p;
+      const char* pb = (const char*)h_pb_.p;
 
       // classify slots + route OK unary calls per backend
       size_t nb = in.n_clients;
-      std::vector<std::vector<H2GrpcClient::RawCall>> per_be(nb);
+      CallsPerBackend per_be(nb);
       std::vector<std::vector<int>> slots_be(nb);
       for (int i = 0; i < n; ++i) {
         SlotOut& so = out->slots[i];
@@ -937,41 +796,24 @@ class Engine : public spanapi::ISpanExecutor {
         if (st == E_OK && (rs[i].flags & SR_SERVER_STREAMING)) {
           // request wire OUT now: decode compaction reuses h_pb_
           so.kind = K_PY_STREAM;
-          so.aux.assign((const char*)pb + rs[i].pb_off, rs[i].pb_len);
-          continue;
-        }
-        if (st == E_OK) {
-          int tool = rs[i].tool_idx;
-          if (tool < 0 || tool >= (int)tool_paths_.size() || nb == 0) {
-            so.kind = K_PY_ENC_FALLBACK;
-            continue;
-          }
-          size_t be = tool < (int)tool_backend_.size()
-                          ? (size_t)tool_backend_[tool] % nb
-                          : 0;
-          const std::string& path = tool_paths_[tool];
-          per_be[be].push_back(H2GrpcClient::RawCall{
-              path.data(), path.size(), pb + rs[i].pb_off, rs[i].pb_len,
-              (in.metas && in.metas[i] && !in.metas[i]->empty())
-                  ? in.metas[i]
-                  : nullptr});
-          slots_be[be].push_back(i);
-          so.kind = K_FINAL;  // provisional until decode verdict
-          continue;
-        }
-        if (st == E_NOT_TOOLCALL) {
+          so.aux.assign(pb + rs[i].pb_off, rs[i].pb_len);
+        } else if (st == E_OK) {
+          // K_FINAL is provisional until the decode verdict
+          so.kind = route_unary(i, in.metas ? in.metas[i] : nullptr, per_be,
+                                slots_be)
+                        ? K_FINAL
+                        : K_PY_ENC_FALLBACK;
+        } else if (st == E_NOT_TOOLCALL) {
           so.kind = K_PY_NOT_TOOLCALL;
-          continue;
-        }
-        if (st == E_UNSUPPORTED || st == E_OVERFLOW) {
+        } else if (st == E_UNSUPPORTED || st == E_OVERFLOW) {
           so.kind = K_PY_ENC_FALLBACK;
-          continue;
+        } else {
+          so.kind = K_ERR_FINAL;
+          int code;
+          const char* msg;
+          status_to_rpc(st, &code, &msg);
+          build_rpc_error(so.aux, i, code, msg);
         }
-        so.kind = K_ERR_FINAL;
-        int code;
-        const char* msg;
-        status_to_rpc(st, &code, &msg);
-        build_rpc_error(so.aux, i, code, msg);
       }
 
       // invoke (pure C++; the h2 clients block until their batch resolves)
@@ -985,102 +827,34 @@ class Engine : public spanapi::ISpanExecutor {
       out->inv_ms =
           std::chrono::duration<double, std::milli>(t2 - t1).count();
 
-      // parse + stage responses for decode (frame rules match process_span)
-      uint32_t* resp_off = (uint32_t*)h_off_.p;
-      uint32_t* final_off = resp_off + (n + 1);
-      uint32_t* scratch_off = resp_off + 2 * (n + 1);
-      int32_t* h_aux = (int32_t*)h_aux_.p;
-      std::vector<const std::string*> resp_ptr(n, nullptr);
+      // parse the replies, then stage the delivered payloads for decode
+      std::vector<Payload> resp(n);
       for (size_t b = 0; b < nb; ++b) {
         for (size_t k = 0; k < slots_be[b].size(); ++k) {
           int i = slots_be[b][k];
           auto& r = res_be[b][k];
-          int status = std::get<0>(r);
-          const std::string& data = std::get<1>(r);
-          size_t plen = 0, poff = 0;
-          bool compressed = false, truncated = false;
-          if (!data.empty()) {
-            if (data.size() >= 5) {
-              compressed = data[0] != 0;
-              uint32_t len;
-              memcpy(&len, data.data() + 1, 4);
-              len = ntohl(len);
-              if (data.size() >= 5 + (size_t)len) {
-                poff = 5;
-                plen = len;
-              } else {
-                truncated = true;
-              }
-            } else {
-              truncated = true;
-            }
-          }
-          const char* local_err = nullptr;
-          if (status < 0) {
-            status = 2;
-            local_err = std::get<2>(r).empty()
-                            ? "stream closed without grpc-status"
-                            : std::get<2>(r).c_str();
-          } else if (status == 0 && compressed) {
-            status = 13;
-            local_err = "compressed gRPC response frame not supported";
-          } else if (status == 0 && truncated) {
-            status = 13;
-            local_err = "truncated gRPC frame";
-          }
-          if (status == 0) {
-            resp_ptr[i] = &std::get<1>(res_be[b][k]);
-            rs[i].err_pos = (uint32_t)poff;  // reuse: payload offset
-            rs[i].aux = (int32_t)plen;       // reuse: payload length
+          GrpcReply g =
+              parse_grpc_reply(std::get<0>(r), std::get<1>(r), std::get<2>(r));
+          if (g.status == 0) {
+            resp[i] = {std::get<1>(r).data() + g.off, g.len};
           } else {
             // gRPC failure -> isError tool result, HTTP 200
             // (handler.go:252-259 semantics)
             SlotOut& so = out->slots[i];
             so.kind = K_ERR_FINAL;
-            build_grpc_error(so.aux, i, status,
-                             local_err ? local_err
-                                       : std::get<2>(r).c_str());
+            build_grpc_error(so.aux, i, g.status, g.err);
           }
         }
       }
-      size_t racc = 0, sacc = 0, facc = 0;
-      uint8_t* rdst = (uint8_t*)h_resp_.p;
-      for (int i = 0; i < n; ++i) {
-        size_t len = resp_ptr[i] ? (size_t)rs[i].aux : 0;
-        // a response that would overflow an arena falls back PER SLOT with
-        // its delivered wire: failing the whole span here would force the
-        // caller to either drop or re-invoke already-invoked slots
-        if (resp_ptr[i] &&
-            (racc + len > h_resp_.n || sacc + scratch_cap(len) > d_scratch_.n ||
-             facc + final_cap(len, span_flags_) > d_final_.n)) {
-          SlotOut& so = out->slots[i];
-          so.kind = K_PY_DEC_FALLBACK;
-          so.aux.assign(resp_ptr[i]->data() + rs[i].err_pos, len);
-          resp_ptr[i] = nullptr;
-          len = 0;
-        }
-        resp_off[i] = (uint32_t)racc;
-        scratch_off[i] = (uint32_t)sacc;
-        final_off[i] = (uint32_t)facc;
-        h_aux[i] = (resp_ptr[i] &&
-                    tool_out_msg_.size() > (size_t)rs[i].tool_idx)
-                       ? tool_out_msg_[rs[i].tool_idx]
-                       : 0;
-        h_aux[n + i] = resp_ptr[i] ? 0 : 1;  // skip slots with no response
-        racc += len;
-        sacc += scratch_cap(len);
-        facc += final_cap(len, span_flags_);
-      }
-      resp_off[n] = (uint32_t)racc;
-      scratch_off[n] = (uint32_t)sacc;
-      final_off[n] = (uint32_t)facc;
-      stage_copies(resp_off, n, racc, [&](int i) {
-        size_t len = resp_off[i + 1] - resp_off[i];
-        if (len)
-          std::memcpy(rdst + resp_off[i], resp_ptr[i]->data() + rs[i].err_pos,
-                      len);
+      // a response that would overflow an arena falls back PER SLOT with
+      // its delivered wire: failing the whole span here would force the
+      // caller to either drop or re-invoke already-invoked slots
+      Staged sd = stage_responses(n, resp, [&](int i, const char*) {
+        SlotOut& so = out->slots[i];
+        so.kind = K_PY_DEC_FALLBACK;
+        so.aux.assign(resp[i].p, resp[i].len);
       });
-      run_decode_device(n, racc, facc, true, 0 | span_flags_);
+      run_decode_device(n, sd.resp, sd.fin, true, 0 | span_flags_);
       auto t3 = std::chrono::steady_clock::now();
       out->dec_ms =
           std::chrono::duration<double, std::milli>(t3 - t2).count();
@@ -1093,15 +867,14 @@ class Engine : public spanapi::ISpanExecutor {
       for (int i = 0; i < n; ++i) {
         SlotOut& so = out->slots[i];
         if (so.kind != K_FINAL) continue;
-        if (resp_ptr[i] && dr[i].status == E_OK && dr[i].out_len > 0) {
+        if (resp[i].p && dr[i].status == E_OK && dr[i].out_len > 0) {
           so.off = dr[i].out_off;
           so.len = dr[i].out_len;
-        } else if (resp_ptr[i]) {
+        } else if (resp[i].p) {
           // decode rejected a DELIVERED response: hand the received wire
           // to the host transcoder — never re-invoke
           so.kind = K_PY_DEC_FALLBACK;
-          so.aux.assign(resp_ptr[i]->data() + rs[i].err_pos,
-                        (size_t)rs[i].aux);
+          so.aux.assign(resp[i].p, resp[i].len);
         } else {
           // routed but no response tuple (client size mismatch): internal
           so.kind = K_ERR_FINAL;
@@ -1140,42 +913,124 @@ class Engine : public spanapi::ISpanExecutor {
 
  private:
   // JSON-RPC id token of a slot (raw JSON captured by the encode kernel;
-  // "null" when absent/unparsed — matches the Python path's best effort)
-  void append_id(std::string& out, int slot) {
+  // nullptr, printed as null, when absent/unparsed — matches the Python
+  // path's best effort)
+  const char* id_token(int slot, size_t* len) {
     const SlotResult* rs = (const SlotResult*)h_results_.p;
-    uint32_t len = rs[slot].id_len;
-    if ((rs[slot].flags & SR_ID_IS_MISSING) || len == 0 ||
-        len > (uint32_t)ID_SLOT_BYTES) {
-      out += "null";
-      return;
-    }
-    out.append((const char*)h_id_.p + (size_t)slot * ID_SLOT_BYTES, len);
+    *len = rs[slot].id_len;
+    if ((rs[slot].flags & SR_ID_IS_MISSING) || *len == 0 ||
+        *len > (size_t)ID_SLOT_BYTES)
+      return nullptr;
+    return (const char*)h_id_.p + (size_t)slot * ID_SLOT_BYTES;
   }
-
-  // {"jsonrpc":"2.0","id":ID,"error":{"code":C,"message":"M"}}
   void build_rpc_error(std::string& out, int slot, int code, const char* msg) {
-    out.clear();
-    out += "{\"jsonrpc\":\"2.0\",\"id\":";
-    append_id(out, slot);
-    out += ",\"error\":{\"code\":";
-    out += std::to_string(code);
-    out += ",\"message\":\"";
-    json_escape_append(out, msg, strlen(msg));
-    out += "\"}}";
+    size_t id_len;
+    const char* id = id_token(slot, &id_len);
+    rpc_error_envelope(out, id, id_len, code, msg);
   }
-
-  // gRPC failure -> isError tool result with HTTP 200 (handler.go:252-259;
-  // text format matches engine/batch.py _host_slot)
   void build_grpc_error(std::string& out, int slot, int status,
                         const char* detail) {
-    out.clear();
-    out += "{\"jsonrpc\":\"2.0\",\"id\":";
-    append_id(out, slot);
-    out += ",\"result\":{\"content\":[{\"type\":\"text\",\"text\":\"gRPC error ";
-    out += grpc_status_name(status);
-    out += ": ";
-    json_escape_append(out, detail, strlen(detail));
-    out += "\"}],\"isError\":true}}";
+    size_t id_len;
+    const char* id = id_token(slot, &id_len);
+    grpc_error_envelope(out, id, id_len, status, detail);
+  }
+
+  // ---- host phases shared by process_span and run_span --------------------
+
+  // Lay n request bodies out in h_in_ (offset prefix in h_off_, pb arena
+  // prefix after it) and copy them in.  Returns nullptr, or why the batch
+  // does not fit; each span fails in its own way.
+  const char* stage_bodies(const char* const* bodies, const size_t* lens, int n,
+                           size_t* in_bytes, size_t* pb_bytes) {
+    uint32_t* in_off = (uint32_t*)h_off_.p;
+    uint32_t* pb_off = in_off + (n + 1);
+    size_t acc = 0, pacc = 0;
+    for (int i = 0; i < n; ++i) {
+      if (acc + lens[i] > h_in_.n) return "input exceeds cap_in";
+      in_off[i] = (uint32_t)acc;
+      pb_off[i] = (uint32_t)pacc;
+      acc += lens[i];
+      pacc += pb_cap(lens[i]);
+    }
+    in_off[n] = (uint32_t)acc;
+    pb_off[n] = (uint32_t)pacc;
+    if (pacc > d_pb_.n) return "pb cap exceeded";
+    uint8_t* dst = (uint8_t*)h_in_.p;
+    stage_copies(in_off, n, acc, [&](int i) {
+      if (lens[i]) std::memcpy(dst + in_off[i], bodies[i], lens[i]);
+    });
+    *in_bytes = acc;
+    *pb_bytes = pacc;
+    return nullptr;
+  }
+
+  // Queue encoded slot i (an OK unary call) on its tool's backend.  False
+  // when the slot names no routable tool or there is no backend.
+  bool route_unary(int i, const SlotMeta* meta, CallsPerBackend& per_be,
+                   std::vector<std::vector<int>>& slots_be) {
+    const SlotResult& r = ((const SlotResult*)h_results_.p)[i];
+    size_t nb = per_be.size();
+    int tool = r.tool_idx;
+    if (tool < 0 || tool >= (int)tool_paths_.size() || nb == 0) return false;
+    size_t be = tool < (int)tool_backend_.size()
+                    ? (size_t)tool_backend_[tool] % nb
+                    : 0;
+    const std::string& path = tool_paths_[tool];
+    per_be[be].push_back(H2GrpcClient::RawCall{
+        path.data(), path.size(), (const uint8_t*)h_pb_.p + r.pb_off, r.pb_len,
+        meta && !meta->empty() ? meta : nullptr});
+    slots_be[be].push_back(i);
+    return true;
+  }
+
+  // Lay the delivered payloads (resp[i].p; null = no reply, the slot is
+  // skipped) out in h_resp_ with their scratch and final arena prefixes,
+  // fill msg_idx | skip, and copy the payloads in.  A payload that would
+  // overflow an arena goes to on_overflow(i, which_cap); if that returns,
+  // the slot is staged as skipped.
+  template <typename F>
+  Staged stage_responses(int n, std::vector<Payload>& resp, F&& on_overflow) {
+    const SlotResult* rs = (const SlotResult*)h_results_.p;
+    uint32_t* resp_off = (uint32_t*)h_off_.p;
+    uint32_t* final_off = resp_off + (n + 1);
+    uint32_t* scratch_off = resp_off + 2 * (n + 1);
+    int32_t* h_aux = (int32_t*)h_aux_.p;
+    size_t racc = 0, sacc = 0, facc = 0;
+    for (int i = 0; i < n; ++i) {
+      Payload& p = resp[i];
+      if (p.p) {
+        const char* over = nullptr;
+        if (racc + p.len > h_resp_.n)
+          over = "resp cap";
+        else if (sacc + scratch_cap(p.len) > d_scratch_.n)
+          over = "scratch cap";
+        else if (facc + final_cap(p.len, span_flags_) > d_final_.n)
+          over = "final cap";
+        if (over) {
+          on_overflow(i, over);
+          p = Payload();
+        }
+      }
+      resp_off[i] = (uint32_t)racc;
+      scratch_off[i] = (uint32_t)sacc;
+      final_off[i] = (uint32_t)facc;
+      // the kernels test skip before they read msg_idx
+      h_aux[i] = (p.p && tool_out_msg_.size() > (size_t)rs[i].tool_idx)
+                     ? tool_out_msg_[rs[i].tool_idx]
+                     : 0;
+      h_aux[n + i] = p.p ? 0 : 1;  // skip slots with no response
+      racc += p.len;
+      sacc += scratch_cap(p.len);
+      facc += final_cap(p.len, span_flags_);
+    }
+    resp_off[n] = (uint32_t)racc;
+    scratch_off[n] = (uint32_t)sacc;
+    final_off[n] = (uint32_t)facc;
+    uint8_t* dst = (uint8_t*)h_resp_.p;
+    stage_copies(resp_off, n, racc, [&](int i) {
+      if (resp[i].len) std::memcpy(dst + resp_off[i], resp[i].p, resp[i].len);
+    });
+    return {racc, sacc, facc};
   }
 
   // fan per-slot staging copies across the pool for big batches,
@@ -1232,55 +1087,26 @@ class Engine : public spanapi::ISpanExecutor {
     HIP_CHECK(hipSetDevice(device_));
     // chunked pipeline for big batches (mode 0, no msg_idx): overlap the
     // H2D / D2H slices with the kernels instead of serializing them
+    int cut[PIPE_MAX_CHUNKS + 1];
+    int C = 1;
     if (mode == 0 && !has_idx && n >= 2 && pipe_chunks() > 1 &&
-        in_bytes + pb_bytes >= pipe_min_bytes()) {
-      int cut[PIPE_MAX_CHUNKS + 1];
-      int C = pipe_cuts(h_off, n, pipe_chunks(), cut);
-      if (C > 1) {
-        run_encode_chunked(n, C, cut, n_wg, lim);
-        last_enc_gpu_ms_ = std::chrono::duration<double, std::milli>(
-                               std::chrono::steady_clock::now() - g0)
-                               .count();
-        last_batch_n_ = n;
-        return;
-      }
+        in_bytes + pb_bytes >= pipe_min_bytes())
+      C = pipe_cuts(h_off, n, pipe_chunks(), cut);
+    if (C > 1) {
+      run_encode_chunked(n, C, cut, n_wg, lim);
+    } else {
+      HIP_CHECK(hipMemcpyAsync(d_in_.p, h_in_.p, in_bytes,
+                               hipMemcpyHostToDevice, stream_));
+      launch_encode(0, n, n, has_idx, mode, n_wg, lim);
+      // results + id tokens + pb wire in ONE packed D2H span (ids sit at
+      // rid_off_, pb at the fixed rid_cap_; the gap between used ids and
+      // rid_cap_ is dead bandwidth, far cheaper than a second submission).
+      // The native span's C++ error envelopes need the ids on the host;
+      // mode-0 decode keeps reading the device copies.
+      HIP_CHECK(hipMemcpyAsync(h_rid_.p, d_rid_.p, rid_cap_ + pb_bytes,
+                               hipMemcpyDeviceToHost, stream_));
+      sync_stream();
     }
-    HIP_CHECK(hipMemcpyAsync(d_in_.p, h_in_.p, in_bytes,
-                             hipMemcpyHostToDevice, stream_));
-    // offsets + aux are zero-copy: the kernels read them from pinned host
-    // memory (d_off3_/d_aux2_ are device pointers INTO h_ctrl_)
-    uint32_t* d_off = (uint32_t*)d_off3_.p;  // in_off | pb_off contiguous
-    int blocks = (int)cdiv(n, WPB);
-    if (blocks > 0) {
-      hipLaunchKernelGGL(k_json2pb, dim3(blocks), dim3(WPB * WAVE), 0,
-                         stream_, (const uint8_t*)d_in_.p,
-                         (const uint32_t*)d_off, (uint8_t*)d_pb_.p,
-                         (const uint32_t*)d_off + (n + 1),
-                         (SlotResult*)d_results_.p, (uint8_t*)d_id_slots_.p,
-                         has_idx ? (const int32_t*)d_aux2_.p : nullptr,
-                         tables_, lim, n, mode,
-                         n_wg > 0 ? (const int32_t*)d_aux2_.p : nullptr);
-      HIP_CHECK(hipGetLastError());
-    }
-    if (n_wg > 0) {
-      hipLaunchKernelGGL(k_json2pb_wg, dim3(n), dim3(WG_ENC_WAVES * WAVE), 0,
-                         stream_, (const uint8_t*)d_in_.p,
-                         (const uint32_t*)d_off, (uint8_t*)d_pb_.p,
-                         (const uint32_t*)d_off + (n + 1),
-                         (SlotResult*)d_results_.p, (uint8_t*)d_id_slots_.p,
-                         (uint8_t*)d_scratch_.p, tables_, lim, n,
-                         (const int32_t*)d_aux2_.p, wg_enc_phases(),
-                         mw_scan_on());
-      HIP_CHECK(hipGetLastError());
-    }
-    // results + id tokens + pb wire in ONE packed D2H span (ids sit at
-    // rid_off_, pb at the fixed rid_cap_; the gap between used ids and
-    // rid_cap_ is dead bandwidth, far cheaper than a second submission).
-    // The native span's C++ error envelopes need the ids on the host;
-    // mode-0 decode keeps reading the device copies.
-    HIP_CHECK(hipMemcpyAsync(h_rid_.p, d_rid_.p, rid_cap_ + pb_bytes,
-                             hipMemcpyDeviceToHost, stream_));
-    sync_stream();
     // pure device span (copies+kernel+sync, no GIL-reacquire wait):
     // separates real GPU time from thread contention in the wall split
     last_enc_gpu_ms_ = std::chrono::duration<double, std::milli>(
@@ -1289,16 +1115,46 @@ class Engine : public spanapi::ISpanExecutor {
     last_batch_n_ = n;
   }
 
+  // The encode kernels over slots [lo, lo+m) of an n-slot batch, on
+  // stream_.  Per-slot addressing is absolute through the offset tables,
+  // so a sub-range is shifted per-slot pointers and a smaller count; n
+  // fixes where the pb offset table starts.  Offsets + aux are zero-copy:
+  // the kernels read them from pinned host memory (d_off3_/d_aux2_ are
+  // device pointers INTO h_ctrl_).  aux holds msg_idx when has_idx, and the
+  // wg routing tags when n_wg > 0 (never both, see run_encode_device).
+  void launch_encode(int lo, int m, int n, bool has_idx, int mode, int n_wg,
+                     Limits lim) {
+    const uint8_t* in = (const uint8_t*)d_in_.p;
+    const uint32_t* in_off = (const uint32_t*)d_off3_.p + lo;
+    const uint32_t* pb_off = (const uint32_t*)d_off3_.p + (n + 1) + lo;
+    const int32_t* aux = (const int32_t*)d_aux2_.p + lo;
+    uint8_t* pb = (uint8_t*)d_pb_.p;
+    SlotResult* results = (SlotResult*)d_results_.p + lo;
+    uint8_t* ids = (uint8_t*)d_id_slots_.p + (size_t)lo * ID_SLOT_BYTES;
+    int blocks = (int)cdiv(m, WPB);
+    if (blocks > 0) {
+      hipLaunchKernelGGL(k_json2pb, dim3(blocks), dim3(WPB * WAVE), 0,
+                         stream_, in, in_off, pb, pb_off, results, ids,
+                         has_idx ? aux : nullptr, tables_, lim, m, mode,
+                         n_wg > 0 ? aux : nullptr);
+      HIP_CHECK(hipGetLastError());
+    }
+    if (n_wg > 0) {
+      hipLaunchKernelGGL(k_json2pb_wg, dim3(m), dim3(WG_ENC_WAVES * WAVE), 0,
+                         stream_, in, in_off, pb, pb_off, results, ids,
+                         (uint8_t*)d_scratch_.p, tables_, lim, m, aux,
+                         wg_enc_phases(), mw_scan_on());
+      HIP_CHECK(hipGetLastError());
+    }
+  }
+
   // Chunked encode (mode 0, no msg_idx — the serving/wide shapes): chunk
   // c+1's input H2D (stream2_) and chunk c-1's pb/results D2H (stream3_)
-  // chunk c's kernels run on stream_.  All kernels stay on ONE stream
+  // overlap chunk c's kernels on stream_.  All kernels stay on ONE stream
   // (serialized — no extra kernel-queue contention); only copies overlap.
-  // Per-item addressing is absolute through the offset tables, so a
-  // sub-range launch is shifted pointers + a smaller n.
   void run_encode_chunked(int n, int C, const int* cut, int n_wg, Limits lim) {
     uint32_t* h_off = (uint32_t*)h_off_.p;
     const uint32_t* h_pb_off = h_off + (n + 1);
-    uint32_t* d_off = (uint32_t*)d_off3_.p;  // zero-copy (pinned host)
     for (int c = 0; c < C; ++c) {
       const int lo = cut[c], hi = cut[c + 1], m = hi - lo;
       const size_t a = h_off[lo], b = h_off[hi];
@@ -1307,29 +1163,7 @@ class Engine : public spanapi::ISpanExecutor {
                                  b - a, hipMemcpyHostToDevice, stream2_));
       HIP_CHECK(hipEventRecord(ev_h2d_[c], stream2_));
       HIP_CHECK(hipStreamWaitEvent(stream_, ev_h2d_[c], 0));
-      int blocks = (int)cdiv(m, WPB);
-      if (blocks > 0) {
-        hipLaunchKernelGGL(
-            k_json2pb, dim3(blocks), dim3(WPB * WAVE), 0, stream_,
-            (const uint8_t*)d_in_.p, (const uint32_t*)d_off + lo,
-            (uint8_t*)d_pb_.p, (const uint32_t*)d_off + (n + 1) + lo,
-            (SlotResult*)d_results_.p + lo,
-            (uint8_t*)d_id_slots_.p + (size_t)lo * ID_SLOT_BYTES, nullptr,
-            tables_, lim, m, 0,
-            n_wg > 0 ? (const int32_t*)d_aux2_.p + lo : nullptr);
-        HIP_CHECK(hipGetLastError());
-      }
-      if (n_wg > 0) {
-        hipLaunchKernelGGL(
-            k_json2pb_wg, dim3(m), dim3(WG_ENC_WAVES * WAVE), 0, stream_,
-            (const uint8_t*)d_in_.p, (const uint32_t*)d_off + lo,
-            (uint8_t*)d_pb_.p, (const uint32_t*)d_off + (n + 1) + lo,
-            (SlotResult*)d_results_.p + lo,
-            (uint8_t*)d_id_slots_.p + (size_t)lo * ID_SLOT_BYTES,
-            (uint8_t*)d_scratch_.p, tables_, lim, m,
-            (const int32_t*)d_aux2_.p + lo, wg_enc_phases(), mw_scan_on());
-        HIP_CHECK(hipGetLastError());
-      }
+      launch_encode(lo, m, n, false, 0, n_wg, lim);
       HIP_CHECK(hipEventRecord(ev_krn_[c], stream_));
       HIP_CHECK(hipStreamWaitEvent(stream3_, ev_krn_[c], 0));
       const size_t pa = h_pb_off[lo], pe = h_pb_off[hi];
@@ -1361,6 +1195,63 @@ class Engine : public spanapi::ISpanExecutor {
     return py::make_tuple(results, pb_view);
   }
 
+  // The decode kernels over slots [lo, lo+m) of an n-slot batch, on
+  // stream_ (see launch_encode).  n fixes where the final and scratch
+  // offset tables and the skip array start.  n_wg > 0 implies mode == 0
+  // and has_skip (see run_decode_device).
+  void launch_decode(int lo, int m, int n, bool has_skip, int mode, int n_wg) {
+    const uint8_t* resp = (const uint8_t*)d_resp_.p;
+    const uint32_t* resp_off = (const uint32_t*)d_off3_.p + lo;
+    const uint32_t* final_off = (const uint32_t*)d_off3_.p + (n + 1) + lo;
+    const uint32_t* scratch_off =
+        (const uint32_t*)d_off3_.p + 2 * (n + 1) + lo;
+    const int32_t* msg_idx = (const int32_t*)d_aux2_.p + lo;
+    const int32_t* skip =
+        has_skip ? (const int32_t*)d_aux2_.p + n + lo : nullptr;
+    const uint8_t* ids =
+        (const uint8_t*)d_id_slots_.p + (size_t)lo * ID_SLOT_BYTES;
+    const SlotResult* enc = (mode & DM_KIND) == 0
+                                ? (const SlotResult*)d_results_.p + lo
+                                : nullptr;
+    uint8_t* scratch = (uint8_t*)d_scratch_.p;
+    uint8_t* fin = (uint8_t*)d_final_.p;
+    DecodeResult* results = (DecodeResult*)d_dec_results_.p + lo;
+    int blocks = (int)cdiv(m, WPB);
+    if (blocks > 0) {
+      hipLaunchKernelGGL(k_pb2json, dim3(blocks), dim3(WPB * WAVE), 0,
+                         stream_, resp, resp_off, msg_idx, ids, enc, scratch,
+                         scratch_off, fin, final_off, results, skip, tables_,
+                         m, mode);
+      HIP_CHECK(hipGetLastError());
+    }
+    if (n_wg > 0) {
+      hipLaunchKernelGGL(k_pb2json_wg, dim3(m), dim3(WG_DEC_WAVES * WAVE), 0,
+                         stream_, resp, resp_off, msg_idx, ids, enc, scratch,
+                         scratch_off, fin, final_off, results, skip, tables_,
+                         m, wg_phases());
+      HIP_CHECK(hipGetLastError());
+    }
+  }
+
+  // Chunked decode (envelope kind with a skip array — the serving/wide
+  // shapes): chunk c+1's response H2D on stream2_ overlaps chunk c's
+  // kernels on stream_ (see run_encode_chunked).  The caller issues the
+  // compact/D2H tail once, after the last chunk.
+  void run_decode_chunked(int n, int C, const int* cut, int mode, int n_wg) {
+    const uint32_t* h_off = (const uint32_t*)h_off_.p;
+    for (int c = 0; c < C; ++c) {
+      const int lo = cut[c], hi = cut[c + 1], m = hi - lo;
+      const size_t a = h_off[lo], b = h_off[hi];
+      if (b > a)
+        HIP_CHECK(hipMemcpyAsync((uint8_t*)d_resp_.p + a,
+                                 (uint8_t*)h_resp_.p + a, b - a,
+                                 hipMemcpyHostToDevice, stream2_));
+      HIP_CHECK(hipEventRecord(ev_h2d_[c], stream2_));
+      HIP_CHECK(hipStreamWaitEvent(stream_, ev_h2d_[c], 0));
+      launch_decode(lo, m, n, true, mode, n_wg);
+    }
+  }
+
   // Device-only decode (no GIL use, callable from native threads).
   // expects: h_resp_ staged, h_off_ = resp/final/scratch offsets,
   // h_aux_ = msg_idx (+ skip at offset n when has_skip)
@@ -1386,87 +1277,20 @@ class Engine : public spanapi::ISpanExecutor {
     }
     auto g0 = std::chrono::steady_clock::now();
     HIP_CHECK(hipSetDevice(device_));
-    // resp_off | final_off | scratch_off contiguous, one copy; same for
-    // msg_idx | skip
     uint32_t* d_off = (uint32_t*)d_off3_.p;
-    int32_t* d_aux = (int32_t*)d_aux2_.p;
-    // chunked pipeline for big response batches: resp H2D slices on
-    // stream2_ overlap the per-chunk kernels on stream_ (see
-    // run_encode_chunked; the compact/D2H tail below is shared)
-    bool chunked = false;
+    // chunked pipeline for big response batches; the compact/D2H tail
+    // below is shared
+    int cut[PIPE_MAX_CHUNKS + 1];
+    int C = 1;
     if (kind == 0 && has_skip && n >= 2 && pipe_chunks() > 1 &&
-        resp_bytes >= pipe_min_bytes()) {
-      int cut[PIPE_MAX_CHUNKS + 1];
-      int C = pipe_cuts(h_off, n, pipe_chunks(), cut);
-      if (C > 1) {
-        for (int c = 0; c < C; ++c) {
-          const int lo = cut[c], hi = cut[c + 1], m = hi - lo;
-          const size_t a = h_off[lo], b = h_off[hi];
-          if (b > a)
-            HIP_CHECK(hipMemcpyAsync((uint8_t*)d_resp_.p + a,
-                                     (uint8_t*)h_resp_.p + a, b - a,
-                                     hipMemcpyHostToDevice, stream2_));
-          HIP_CHECK(hipEventRecord(ev_h2d_[c], stream2_));
-          HIP_CHECK(hipStreamWaitEvent(stream_, ev_h2d_[c], 0));
-          int cblocks = (int)cdiv(m, WPB);
-          if (cblocks > 0) {
-            hipLaunchKernelGGL(
-                k_pb2json, dim3(cblocks), dim3(WPB * WAVE), 0, stream_,
-                (const uint8_t*)d_resp_.p, (const uint32_t*)d_off + lo,
-                (const int32_t*)d_aux + lo,
-                (const uint8_t*)d_id_slots_.p + (size_t)lo * ID_SLOT_BYTES,
-                (const SlotResult*)d_results_.p + lo, (uint8_t*)d_scratch_.p,
-                (const uint32_t*)d_off + 2 * (n + 1) + lo,
-                (uint8_t*)d_final_.p, (const uint32_t*)d_off + (n + 1) + lo,
-                (DecodeResult*)d_dec_results_.p + lo,
-                (const int32_t*)d_aux + n + lo, tables_, m, mode);
-            HIP_CHECK(hipGetLastError());
-          }
-          if (n_wg > 0) {
-            hipLaunchKernelGGL(
-                k_pb2json_wg, dim3(m), dim3(WG_DEC_WAVES * WAVE), 0, stream_,
-                (const uint8_t*)d_resp_.p, (const uint32_t*)d_off + lo,
-                (const int32_t*)d_aux + lo,
-                (const uint8_t*)d_id_slots_.p + (size_t)lo * ID_SLOT_BYTES,
-                (const SlotResult*)d_results_.p + lo, (uint8_t*)d_scratch_.p,
-                (const uint32_t*)d_off + 2 * (n + 1) + lo,
-                (uint8_t*)d_final_.p, (const uint32_t*)d_off + (n + 1) + lo,
-                (DecodeResult*)d_dec_results_.p + lo,
-                (const int32_t*)d_aux + n + lo, tables_, m, wg_phases());
-            HIP_CHECK(hipGetLastError());
-          }
-        }
-        chunked = true;
-      }
-    }
-    if (!chunked) {
+        resp_bytes >= pipe_min_bytes())
+      C = pipe_cuts(h_off, n, pipe_chunks(), cut);
+    if (C > 1) {
+      run_decode_chunked(n, C, cut, mode, n_wg);
+    } else {
       HIP_CHECK(hipMemcpyAsync(d_resp_.p, h_resp_.p, resp_bytes,
                                hipMemcpyHostToDevice, stream_));
-      // offsets + msg_idx/skip are zero-copy (pinned host ctrl block)
-    }
-    int blocks = chunked ? 0 : (int)cdiv(n, WPB);
-    if (blocks > 0) {
-      hipLaunchKernelGGL(
-          k_pb2json, dim3(blocks), dim3(WPB * WAVE), 0, stream_,
-          (const uint8_t*)d_resp_.p, (const uint32_t*)d_off,
-          (const int32_t*)d_aux, (const uint8_t*)d_id_slots_.p,
-          kind == 0 ? (const SlotResult*)d_results_.p : nullptr,
-          (uint8_t*)d_scratch_.p, (const uint32_t*)d_off + 2 * (n + 1),
-          (uint8_t*)d_final_.p, (const uint32_t*)d_off + (n + 1),
-          (DecodeResult*)d_dec_results_.p,
-          has_skip ? (const int32_t*)d_aux + n : nullptr, tables_, n, mode);
-      HIP_CHECK(hipGetLastError());
-    }
-    if (n_wg > 0 && !chunked) {
-      hipLaunchKernelGGL(
-          k_pb2json_wg, dim3(n), dim3(WG_DEC_WAVES * WAVE), 0, stream_,
-          (const uint8_t*)d_resp_.p, (const uint32_t*)d_off,
-          (const int32_t*)d_aux, (const uint8_t*)d_id_slots_.p,
-          (const SlotResult*)d_results_.p, (uint8_t*)d_scratch_.p,
-          (const uint32_t*)d_off + 2 * (n + 1), (uint8_t*)d_final_.p,
-          (const uint32_t*)d_off + (n + 1), (DecodeResult*)d_dec_results_.p,
-          (const int32_t*)d_aux + n, tables_, n, wg_phases());
-      HIP_CHECK(hipGetLastError());
+      launch_decode(0, n, n, has_skip, mode, n_wg);
     }
     // Device-side compaction: k_tight_scan rewrites out_off to a packed
     // layout and k_compact_out gathers the used bytes, all before the

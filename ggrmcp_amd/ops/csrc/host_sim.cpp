@@ -7,8 +7,10 @@
 
 #include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
+#include <pybind11/stl.h>
 
 #include <cstring>
+#include <optional>
 #include <string>
 #include <vector>
 
@@ -18,6 +20,7 @@
 
 #include "json2pb.hip"
 #include "pb2json.hip"
+#include "span_host.h"
 
 SimDim3 threadIdx, blockIdx, blockDim, gridDim;
 
@@ -164,4 +167,32 @@ PYBIND11_MODULE(_hostsim, m) {
       .def("decode", &HostEngine::decode, py::arg("data"), py::arg("resp_off"),
            py::arg("scratch_off"), py::arg("final_off"), py::arg("msg_idx"),
            py::arg("skip") = py::none(), py::arg("mode") = 0);
+
+  // the native spans' pure host pieces (span_host.h), for the CPU tier
+  m.def("grpc_reply", [](int status, const std::string& data,
+                         const std::string& msg) {
+    spanhost::GrpcReply g = spanhost::parse_grpc_reply(status, data, msg);
+    return py::make_tuple(g.status, g.off, g.len,
+                          g.err ? py::object(py::str(g.err)) : py::none());
+  }, py::arg("status"), py::arg("data"), py::arg("msg"));
+  m.def("status_to_rpc", [](int status) {
+    int code;
+    const char* msg;
+    spanhost::status_to_rpc(status, &code, &msg);
+    return py::make_tuple(code, msg);
+  }, py::arg("status"));
+  m.def("rpc_error_envelope", [](std::optional<std::string> id, int code,
+                                 const std::string& msg) {
+    std::string out;
+    spanhost::rpc_error_envelope(out, id ? id->data() : nullptr,
+                                 id ? id->size() : 0, code, msg.c_str());
+    return py::bytes(out);
+  }, py::arg("id"), py::arg("code"), py::arg("msg"));
+  m.def("grpc_error_envelope", [](std::optional<std::string> id, int status,
+                                  const std::string& detail) {
+    std::string out;
+    spanhost::grpc_error_envelope(out, id ? id->data() : nullptr,
+                                  id ? id->size() : 0, status, detail.c_str());
+    return py::bytes(out);
+  }, py::arg("id"), py::arg("status"), py::arg("detail"));
 }

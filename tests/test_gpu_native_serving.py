@@ -137,6 +137,109 @@ def test_native_span_decode_fallback_single_invoke(native_gateway):
     assert after - before == 1, "fallback must not re-invoke" 
 
 
+def _pipelined(port, bodies):
+    """POST every body on one connection in a single send (HTTP/1.1
+    pipelining), so the reactor parses them in one pass and hands them to
+    the span executor together; returns the response bodies in order."""
+    import socket
+
+    req = b"".join(
+        b"POST / HTTP/1.1\r\nHost: x\r\nContent-Type: application/json\r\n"
+        b"Content-Length: %d\r\n\r\n%s" % (len(b), b) for b in bodies)
+    out = []
+    with socket.create_connection(("127.0.0.1", port), timeout=20) as s:
+        s.sendall(req)
+        buf = b""
+        while len(out) < len(bodies):
+            head, sep, rest = buf.partition(b"\r\n\r\n")
+            clen = None
+            if sep:
+                for line in head.split(b"\r\n")[1:]:
+                    k, _, v = line.partition(b":")
+                    if k.strip().lower() == b"content-length":
+                        clen = int(v)
+            if clen is not None and len(rest) >= clen:
+                assert head.startswith(b"HTTP/1.1 200"), head
+                out.append(rest[:clen])
+                buf = rest[clen:]
+                continue
+            chunk = s.recv(1 << 20)
+            assert chunk, "connection closed early"
+            buf += chunk
+    return out
+
+
+def test_both_span_paths_answer_alike(native_gateway):
+    """One batch through Engine.process_span (GpuPipeline.process_batch with
+    wire clients) and through Engine.run_span (the native frontend), same
+    backend: every slot's response is the same JSON.  The two spans share
+    their host phases and kernel launchers but keep their own error policy
+    and envelope writers (C++ in run_span, Python for process_span's error
+    slots), so each slot kind is compared.  Batch sizes: 1; WPB + 1 = 5 (a
+    partial block); and all kinds next to a 64 KB echo, whose response is
+    over the workgroup-decode threshold, so both decode kernels run in one
+    span."""
+    import random
+
+    from ggrmcp_amd.utils.synthetic import wide_payload
+
+    gw, port, pipeline = native_gateway[:3]
+
+    def call(tool, args, **env):
+        d = {"jsonrpc": "2.0", "id": 1, "method": "tools/call",
+             "params": {"name": tool, "arguments": args}}
+        d.update(env)
+        return d
+
+    hello = "hello_helloservice_sayhello"
+    ok_1k = call(hello, {"name": "n" * 900}, id=7)
+    assert 900 < len(json.dumps(ok_1k)) < 1100
+    bad_arg = call(hello, {"nope": 1}, id=8)
+    bad_tool = call("no_such_tool", {}, id=9)
+    not_call = {"jsonrpc": "2.0", "id": 10, "method": "tools/list"}
+    no_id = call(hello, {"name": "anon"})
+    del no_id["id"]
+    quoted_id = call(hello, {"name": "q"}, id='a"b')
+    stream = call("bench_echoservice_streamecho",
+                  {"f01String": "s", "f02Int32": 3}, id=11)
+    grpc_err = call(hello, {"name": "error"}, id="err-2")
+    big = call("bench_echoservice_echo",
+               wide_payload(random.Random(7), target_bytes=64 * 1024), id=12)
+
+    batches = [
+        [ok_1k],
+        [ok_1k, bad_arg, bad_tool, not_call, no_id],
+        [big, ok_1k, bad_arg, bad_tool, not_call, no_id, quoted_id, stream,
+         grpc_err],
+    ]
+    for batch in batches:
+        bodies = [json.dumps(b).encode() for b in batch]
+        st0 = gw._fe.native_stats()
+        via_run_span = _pipelined(port, bodies)
+        st1 = gw._fe.native_stats()
+        spans = st1["batches"] - st0["batches"]
+        print(len(bodies), "slots in", spans, "run_span call(s)")
+        assert st1["requests"] - st0["requests"] == len(bodies)
+        if sum(map(len, bodies)) < 16384:
+            # one TCP segment on loopback: parsed and dispatched together
+            assert spans == 1
+        via_process_span = pipeline.process_batch(bodies, timeout_s=15.0)
+        assert len(via_process_span) == len(via_run_span) == len(bodies)
+        for req, a, b in zip(batch, via_process_span, via_run_span):
+            assert json.loads(a) == json.loads(b), req.get("id")
+    # the slots are what they are meant to be
+    got = [json.loads(b) for b in via_run_span]
+    assert got[0]["result"]["isError"] is False and got[0]["id"] == 12
+    assert got[2]["error"]["code"] == -32602
+    assert got[3]["error"]["code"] == -32601
+    assert "tools" in got[4]["result"]
+    assert got[5]["id"] is None and got[5]["result"]["isError"] is False
+    assert got[6]["id"] == 'a"b'
+    assert len(got[7]["result"]["content"]) == 3
+    assert got[8]["result"]["content"][0]["text"].startswith(
+        "gRPC error INVALID_ARGUMENT")
+
+
 def test_serving_concurrent_sessions(native_gateway):
     gw, port, pipeline = native_gateway[:3]
     errs = []

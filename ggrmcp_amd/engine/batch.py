@@ -196,6 +196,13 @@ class GpuEngine:
         self._eng.set_structured_content(bool(on))
         self.structured_flags = (DM_UNPOPULATED | DM_STRUCTURED) if on else 0
 
+    @property
+    def wg_decode_slots(self) -> int:
+        """Slots this engine has routed to the workgroup decode kernel, ever.
+        Such a slot's ``DecodeResult.pad`` says which pass answered: 1 = the
+        item walk, 2 = the in-block classic pass (0 = ``k_pb2json``)."""
+        return int(self._eng.wg_decode_slots)
+
     # -- low-level batch ops -------------------------------------------------
 
     def encode_batch(

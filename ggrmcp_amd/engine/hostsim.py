@@ -10,14 +10,29 @@ why WAVE=1 execution is faithful.
 from __future__ import annotations
 
 import importlib
+import os
 import sys
 from pathlib import Path
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .batch import DECODE_DTYPE, DM_STRUCTURED, E_OK, SLOT_DTYPE, _offsets
+from .batch import (DECODE_DTYPE, DM_STRUCTURED, DM_UNPOPULATED, E_OK,
+                    SLOT_DTYPE, _offsets)
 from .tables import compile_tables
+
+
+# common.h WG_DEC_*: the workgroup decode kernel's threshold and the scratch
+# a routed slot gets on top (engine.cpp scratch_cap)
+WG_DEC_MIN_BYTES = 16384
+WG_DEC_EXTRA = 256 * 768 + 1024
+WG_DEC_FILL = 8192
+
+
+def wg_dec_min() -> int:
+    """engine.cpp wg_dec_min(): GGRMCP_WG_DEC_MIN overrides the threshold."""
+    e = os.environ.get("GGRMCP_WG_DEC_MIN")
+    return int(e) if e else WG_DEC_MIN_BYTES
 
 
 def load_module():
@@ -30,7 +45,10 @@ def load_module():
 class HostSimEngine:
     """CPU twin of GpuEngine (same tables, same buffer layout)."""
 
-    def __init__(self, tools: Dict[str, Any]) -> None:
+    def __init__(self, tools: Dict[str, Any], wg: bool = False) -> None:
+        # wg: decode_batch's default — also run the workgroup decode kernel's
+        # host driver over the envelope slots the engine would route to it
+        self.wg = wg
         mod = load_module()
         self.tables = compile_tables(tools)
         t = self.tables
@@ -72,19 +90,35 @@ class HostSimEngine:
         msg_indices: Sequence[int],
         mode: int,
         skip: Optional[Sequence[bool]] = None,
+        wg: Optional[bool] = None,
     ) -> Tuple[np.ndarray, List[Optional[bytes]]]:
+        """``wg`` (default: the constructor's): envelope slots of
+        ``wg_dec_min()`` bytes or more get the scratch the engine gives a
+        routed slot and are answered by ``k_pb2json_wg``'s host driver; their
+        ``pad`` is 1 (item walk) or 2 (in-block classic pass)."""
+        wg = (self.wg if wg is None else wg) and (mode & 3) == 0
         skips = [1 if (p is None or (skip is not None and skip[i])) else 0
                  for i, p in enumerate(payloads)]
         safe = [p if p is not None else b"" for p in payloads]
         data = b"".join(safe)
         lens = [len(p) for p in safe]
         resp_off = _offsets(lens)
-        scratch_off = _offsets([n * 8 + 1024 for n in lens], align=16)
+        scratch = [n * 8 + 1024 for n in lens]
+        if wg:
+            thr = wg_dec_min()
+            for i, n in enumerate(lens):
+                if not skips[i] and n >= thr:
+                    skips[i] = 2
+                    scratch[i] += WG_DEC_EXTRA + (
+                        WG_DEC_FILL if mode & DM_UNPOPULATED else 0)
+        scratch = [(n + 15) & ~15 for n in scratch]
+        scratch_off = _offsets(scratch)
         # a structured envelope holds the JSON twice: escaped and raw
-        extra = [n * 8 + 1024 if mode & DM_STRUCTURED else 0 for n in lens]
+        extra = [x if mode & DM_STRUCTURED else 0 for x in scratch]
         final_off = _offsets([n * 16 + 2048 + x for n, x in zip(lens, extra)],
                              align=16)
-        raw, fin = self._eng.decode(
+        decode = self._eng.decode_wg if wg else self._eng.decode
+        raw, fin = decode(
             data, resp_off, scratch_off, final_off,
             np.asarray(msg_indices, dtype=np.int32),
             np.asarray(skips, dtype=np.int32), mode,
@@ -92,7 +126,7 @@ class HostSimEngine:
         results = np.frombuffer(raw.tobytes(), dtype=DECODE_DTYPE)
         out: List[Optional[bytes]] = []
         for i, r in enumerate(results):
-            if skips[i] or r["status"] != E_OK:
+            if skips[i] == 1 or r["status"] != E_OK:
                 out.append(None)
             else:
                 out.append(fin[r["out_off"] : r["out_off"] + r["out_len"]])

@@ -43,7 +43,7 @@ def _common_flags():
 
 def build_jsonproto(verbose: bool = True, force: bool = False) -> Path:
     sources = [CSRC / "engine.cpp", CSRC / "json2pb.hip", CSRC / "pb2json.hip",
-               CSRC / "common.h", CSRC / "h2grpc_impl.h", CSRC / "span_api.h",
+               CSRC / "pb2json_wg.h", CSRC / "common.h", CSRC / "h2grpc_impl.h", CSRC / "span_api.h",
                CSRC / "span_host.h"]
     if not force and not _needs(SO_PATH, sources):
         return SO_PATH
@@ -81,7 +81,7 @@ HOSTSIM_SO_PATH = OPS_DIR / "_hostsim.so"
 def build_hostsim(verbose: bool = True, force: bool = False) -> Path:
     """Single-lane CPU build of the kernels (csrc/host_shim.h)."""
     sources = [CSRC / "host_sim.cpp", CSRC / "json2pb.hip", CSRC / "pb2json.hip",
-               CSRC / "common.h", CSRC / "host_shim.h", CSRC / "span_host.h"]
+               CSRC / "pb2json_wg.h", CSRC / "common.h", CSRC / "host_shim.h", CSRC / "span_host.h"]
     if not force and not _needs(HOSTSIM_SO_PATH, sources):
         return HOSTSIM_SO_PATH
     cxx = os.environ.get("CXX", "g++")

@@ -158,6 +158,8 @@ struct __attribute__((packed)) DecodeResult {
   int32_t status;
   uint32_t out_off;  // final response bytes in the output arena
   uint32_t out_len;
+  // which decode pass answered: 0 = k_pb2json, 1 = k_pb2json_wg's items,
+  // 2 = k_pb2json_wg's in-block classic pass
   uint32_t pad;
 };
 static_assert(sizeof(DecodeResult) == 16, "DecodeResult layout");
@@ -439,6 +441,12 @@ constexpr uint32_t WG_DEC_ITEM_PAD = 256;
 constexpr uint32_t WG_DEC_EXTRA =
     WG_DEC_ITEM_PAD * (uint32_t)WG_DEC_MAX_ITEMS + 1024;
 constexpr int WG_DEC_WAVES = 16;  // waves per request workgroup
+// With DM_UNPOPULATED a routed slot gets WG_DEC_FILL more scratch, past every
+// item region: the defaults of the top message's absent fields (the "fill
+// items") are printed there, not in the 256-byte pad of a neighbouring item.
+// All 64 defaults of bench.Wide64 print in ~1.3 KB; a top message whose
+// defaults outgrow the area leaves with E_OVERFLOW like any other slot.
+constexpr uint32_t WG_DEC_FILL = 8192;
 
 // Workgroup-cooperative ENCODE (k_json2pb_wg): JSON-RPC requests at least
 // WG_ENC_MIN_BYTES long split their arguments object into top-level-member

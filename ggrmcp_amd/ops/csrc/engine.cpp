@@ -152,6 +152,15 @@ inline size_t scratch_cap(size_t wire_len) {
           (wire_len >= wg_dec_min() ? (size_t)WG_DEC_EXTRA : 0) + 15) &
          ~(size_t)15;
 }
+// with DM_UNPOPULATED a slot the workgroup kernel takes also gets the fill
+// area (common.h WG_DEC_FILL).  With the flag clear no offset moves.
+inline size_t scratch_cap(size_t wire_len, int mode) {
+  return scratch_cap(wire_len) +
+         ((mode & DM_UNPOPULATED) && (mode & DM_KIND) == 0 &&
+                  wire_len >= wg_dec_min()
+              ? (size_t)WG_DEC_FILL
+              : 0);
+}
 inline size_t final_cap(size_t wire_len) {
   return (wire_len * 16 + 2048 + 15) & ~(size_t)15;
 }
@@ -160,7 +169,7 @@ inline size_t final_cap(size_t wire_len) {
 // the scratch arena can hold.  Without the flag the layout does not move.
 inline size_t final_cap(size_t wire_len, int mode) {
   return final_cap(wire_len) +
-         ((mode & DM_STRUCTURED) ? scratch_cap(wire_len) : 0);
+         ((mode & DM_STRUCTURED) ? scratch_cap(wire_len, mode) : 0);
 }
 
 }  // namespace
@@ -598,7 +607,7 @@ class Engine : public spanapi::ISpanExecutor {
       final_off[i] = (uint32_t)facc;
       if (len) std::memcpy(dst + acc, ptr, len);
       acc += len;
-      sacc += scratch_cap(len);
+      sacc += scratch_cap(len, mode);
       facc += final_cap(len, mode);
       if (has_skip) h_aux[n + i] = skipped ? 1 : 0;
     }
@@ -910,6 +919,8 @@ class Engine : public spanapi::ISpanExecutor {
 
   int device() const { return device_; }
   int max_batch() const { return max_batch_; }
+  // cumulative count of slots routed to k_pb2json_wg (+= n_wg per batch)
+  uint64_t wg_decode_slots() const { return wg_decode_slots_; }
 
  private:
   // JSON-RPC id token of a slot (raw JSON captured by the encode kernel;
@@ -1002,7 +1013,7 @@ class Engine : public spanapi::ISpanExecutor {
         const char* over = nullptr;
         if (racc + p.len > h_resp_.n)
           over = "resp cap";
-        else if (sacc + scratch_cap(p.len) > d_scratch_.n)
+        else if (sacc + scratch_cap(p.len, span_flags_) > d_scratch_.n)
           over = "scratch cap";
         else if (facc + final_cap(p.len, span_flags_) > d_final_.n)
           over = "final cap";
@@ -1020,7 +1031,7 @@ class Engine : public spanapi::ISpanExecutor {
                      : 0;
       h_aux[n + i] = p.p ? 0 : 1;  // skip slots with no response
       racc += p.len;
-      sacc += scratch_cap(p.len);
+      sacc += scratch_cap(p.len, span_flags_);
       facc += final_cap(p.len, span_flags_);
     }
     resp_off[n] = (uint32_t)racc;
@@ -1197,8 +1208,8 @@ class Engine : public spanapi::ISpanExecutor {
 
   // The decode kernels over slots [lo, lo+m) of an n-slot batch, on
   // stream_ (see launch_encode).  n fixes where the final and scratch
-  // offset tables and the skip array start.  n_wg > 0 implies mode == 0
-  // and has_skip (see run_decode_device).
+  // offset tables and the skip array start.  n_wg > 0 implies kind 0 and
+  // has_skip (see run_decode_device).
   void launch_decode(int lo, int m, int n, bool has_skip, int mode, int n_wg) {
     const uint8_t* resp = (const uint8_t*)d_resp_.p;
     const uint32_t* resp_off = (const uint32_t*)d_off3_.p + lo;
@@ -1228,7 +1239,7 @@ class Engine : public spanapi::ISpanExecutor {
       hipLaunchKernelGGL(k_pb2json_wg, dim3(m), dim3(WG_DEC_WAVES * WAVE), 0,
                          stream_, resp, resp_off, msg_idx, ids, enc, scratch,
                          scratch_off, fin, final_off, results, skip, tables_,
-                         m, wg_phases());
+                         m, mode, wg_phases());
       HIP_CHECK(hipGetLastError());
     }
   }
@@ -1259,14 +1270,13 @@ class Engine : public spanapi::ISpanExecutor {
                          bool has_skip, int mode) {
     uint32_t* h_off = (uint32_t*)h_off_.p;
     int32_t* h_aux = (int32_t*)h_aux_.p;
-    // route big mode-0 responses to the workgroup-cooperative kernel
-    // (skip tag 2): the classic kernel skips them, k_pb2json_wg decodes
-    // one request per workgroup (common.h WG_DEC_*).  It knows neither DM_
-    // flag, hence `mode == 0` and not `kind == 0`: with a flag set, large
-    // responses stay on the classic kernel (correct, slower)
+    // route big envelope (kind 0) responses to the workgroup-cooperative
+    // kernel (skip tag 2): the classic kernel skips them, k_pb2json_wg
+    // decodes one request per workgroup (common.h WG_DEC_*), with the same
+    // DM_ flags
     const int kind = mode & DM_KIND;
     int n_wg = 0;
-    if (mode == 0 && has_skip) {
+    if (kind == 0 && has_skip) {
       uint32_t thr = wg_dec_min();
       for (int i = 0; i < n; ++i) {
         if (h_aux[n + i] == 0 && h_off[i + 1] - h_off[i] >= thr) {
@@ -1275,6 +1285,7 @@ class Engine : public spanapi::ISpanExecutor {
         }
       }
     }
+    wg_decode_slots_ += (uint64_t)n_wg;
     auto g0 = std::chrono::steady_clock::now();
     HIP_CHECK(hipSetDevice(device_));
     uint32_t* d_off = (uint32_t*)d_off3_.p;
@@ -1367,6 +1378,7 @@ class Engine : public spanapi::ISpanExecutor {
   double last_enc_ms_ = 0.0, last_inv_ms_ = 0.0, last_dec_ms_ = 0.0;
   double last_enc_gpu_ms_ = 0.0, last_dec_gpu_ms_ = 0.0;
   int last_batch_n_ = -1;
+  uint64_t wg_decode_slots_ = 0;  // slots routed to k_pb2json_wg, ever
   int span_flags_ = 0;  // DM_* flags OR-ed into the serving spans' decode mode
   bool compact_used_ = false;
   size_t compact_bytes_ = 0;
@@ -1496,5 +1508,6 @@ PYBIND11_MODULE(_jsonproto, m) {
            "opaque ISpanExecutor* for the native HTTP frontend "
            "(span_api.h); the engine must outlive the frontend")
       .def_property_readonly("device", &Engine::device)
-      .def_property_readonly("max_batch", &Engine::max_batch);
+      .def_property_readonly("max_batch", &Engine::max_batch)
+      .def_property_readonly("wg_decode_slots", &Engine::wg_decode_slots);
 }

@@ -33,6 +33,19 @@ static inline uint32_t __shfl(uint32_t v, int, int) { return v; }
 static inline uint64_t __shfl(uint64_t v, int, int) { return v; }
 static inline int __shfl(int v, int, int) { return v; }
 static inline uint32_t __shfl_up(uint32_t, int, int) { return 0; }
+// reduction trees have no step at WAVE=1: never called, must only compile
+static inline uint32_t __shfl_down(uint32_t v, int, int) { return v; }
+// the driver runs one wave at a time, so shared-state atomics are plain
+static inline int atomicAdd(int* p, int v) {
+  int old = *p;
+  *p = old + v;
+  return old;
+}
+static inline int atomicCAS(int* p, int cmp, int v) {
+  int old = *p;
+  if (old == cmp) *p = v;
+  return old;
+}
 static inline uint64_t __ballot(bool p) { return p ? 1ull : 0ull; }
 static inline int __ffsll(long long m) { return __builtin_ffsll(m); }
 static inline bool __all(int p) { return p != 0; }

@@ -87,6 +87,28 @@ class HostEngine {
                    py::array_t<uint32_t> scratch_off,
                    py::array_t<uint32_t> final_off, py::array_t<int32_t> msg_idx,
                    py::object skip, int mode) {
+    return decode_impl(data, resp_off, scratch_off, final_off, msg_idx, skip,
+                       mode, false);
+  }
+
+  // decode, then the workgroup kernel's host driver (wg_decode_host) over
+  // the slots whose skip tag is 2, as Engine::launch_decode does: kind 0 only
+  py::tuple decode_wg(py::buffer data, py::array_t<uint32_t> resp_off,
+                      py::array_t<uint32_t> scratch_off,
+                      py::array_t<uint32_t> final_off,
+                      py::array_t<int32_t> msg_idx, py::object skip, int mode) {
+    if ((mode & DM_KIND) != 0 || skip.is_none())
+      throw std::runtime_error("decode_wg: envelope mode with a skip array");
+    return decode_impl(data, resp_off, scratch_off, final_off, msg_idx, skip,
+                       mode, true);
+  }
+
+ private:
+  py::tuple decode_impl(py::buffer data, py::array_t<uint32_t> resp_off,
+                        py::array_t<uint32_t> scratch_off,
+                        py::array_t<uint32_t> final_off,
+                        py::array_t<int32_t> msg_idx, py::object skip, int mode,
+                        bool wg) {
     py::buffer_info din = data.request();
     auto resp_off_v = resp_off.unchecked<1>();
     int n = (int)resp_off_v.shape(0) - 1;
@@ -107,12 +129,16 @@ class HostEngine {
                 scratch.data(),
                 scratch_off.data(), fin.data(), final_off.data(),
                 results.data(), skip_ptr, n, mode);
+    if (wg)
+      wg_decode_host((const uint8_t*)din.ptr, resp_off.data(), msg_idx.data(),
+                     last_ids_.data(), last_results_.data(), scratch.data(),
+                     scratch_off.data(), fin.data(), final_off.data(),
+                     results.data(), skip_ptr, t_, n, mode);
     py::array_t<uint8_t> res({(py::ssize_t)(n * sizeof(DecodeResult))});
     std::memcpy(res.mutable_data(), results.data(), n * sizeof(DecodeResult));
     return py::make_tuple(res, py::bytes((const char*)fin.data(), fin.size()));
   }
 
- private:
   // drive the kernels one wave (= one request) at a time, WAVE=1 lanes
   void run_json2pb(const uint8_t* in, const uint32_t* in_off, uint8_t* pb,
                    const uint32_t* pb_off, SlotResult* results, uint8_t* ids,
@@ -166,7 +192,10 @@ PYBIND11_MODULE(_hostsim, m) {
            py::arg("enforce") = 1)
       .def("decode", &HostEngine::decode, py::arg("data"), py::arg("resp_off"),
            py::arg("scratch_off"), py::arg("final_off"), py::arg("msg_idx"),
-           py::arg("skip") = py::none(), py::arg("mode") = 0);
+           py::arg("skip") = py::none(), py::arg("mode") = 0)
+      .def("decode_wg", &HostEngine::decode_wg, py::arg("data"),
+           py::arg("resp_off"), py::arg("scratch_off"), py::arg("final_off"),
+           py::arg("msg_idx"), py::arg("skip"), py::arg("mode") = 0);
 
   // the native spans' pure host pieces (span_host.h), for the CPU tier
   m.def("grpc_reply", [](int status, const std::string& data,

@@ -52,7 +52,7 @@ struct DCtx {
   int32_t status;
   int lane;
   // walker option (DM_UNPOPULATED or 0).  Default-initialised so contexts
-  // that never set it (the workgroup kernel's) keep default omission.
+  // that never set it (the output-side ones) keep default omission.
   uint32_t unpop = 0;
 };
 
@@ -1628,8 +1628,11 @@ DEV bool decode_walk(DCtx& c, int top_msg_idx, uint32_t top_end,
       // a field that runs past its message (an Any payload cut short, say)
       // must not hand the parent a cursor inside its next field
       if (c.pos > f.end) return dfail(c, E_PARSE);
-      if (c.unpop && !fill_unpopulated(c, f.msg_idx, f.prev_number,
-                                       0xFFFFFFFFu, &f.first_member))
+      // a bare top frame is one item of the workgroup kernel's join: the
+      // gaps around it are fill items of their own (wgd_scan)
+      if (c.unpop && !(bare_top && sp == 1) &&
+          !fill_unpopulated(c, f.msg_idx, f.prev_number, 0xFFFFFFFFu,
+                            &f.first_member))
         return false;
       if (!(bare_top && sp == 1) && !putc_(c, '}')) return false;
       --sp;
@@ -1661,7 +1664,7 @@ DEV bool decode_walk(DCtx& c, int top_msg_idx, uint32_t top_end,
     }
     // out-of-order / non-adjacent duplicates -> host transcodes
     if (num <= f.prev_number) return dfail(c, E_UNSUPPORTED);
-    if (c.unpop &&
+    if (c.unpop && !(bare_top && sp == 1) &&
         !fill_unpopulated(c, f.msg_idx, f.prev_number, num, &f.first_member))
       return false;
     f.prev_number = num;
@@ -1999,416 +2002,5 @@ extern "C" __global__ void __launch_bounds__(256) k_tight_scan(
 }
 #endif  // GGRMCP_HOST_SIM
 
-#ifndef GGRMCP_HOST_SIM
-// ---------------------------------------------------------------------------
-// k_pb2json_wg — workgroup-per-request decode for LARGE responses
-// (BASELINE config 3: 64 KB payloads).
-//
-// The per-wave walker serializes one request through 64 lanes at a
-// ~26 us/KB floor (a 64 KB response costs ~1.7 ms of wave latency and the
-// whole batch inherits it).  Here one WORKGROUP (WG_DEC_WAVES wave64s)
-// owns one request:
-//   A. one thread scans the top-level wire for contiguous field runs
-//      ("items") — O(#fields), just varint/tag walking;
-//   B. waves grab items dynamically and decode each item with the SAME
-//      decode_walk machinery (bare_top: no surrounding braces) into a
-//      private scratch region, then compute its escaped length;
-//   C. one thread prefix-sums the escaped item lengths into final
-//      offsets (comma-joined, skipping default-omitted empty items);
-//   D. wave 0 writes the JSON-RPC envelope framing while every wave
-//      escape-copies its items into place.
-// Requests the scanner cannot split safely (WKT-typed top message,
-// out-of-order top fields, > WG_DEC_MAX_ITEMS runs) fall back to the
-// classic single-wave mode-0 path inside the same block, preserving
-// exact semantics.  The engine routes only mode-0 slots with
-// wire_len >= WG_DEC_MIN_BYTES here (skip tag == 2).
-// ---------------------------------------------------------------------------
-
-static __device__ const char WG_P1[] = "{\"jsonrpc\":\"2.0\",\"id\":";
-static __device__ const char WG_P2[] =
-    ",\"result\":{\"content\":[{\"type\":\"text\",\"text\":\"";
-static __device__ const char WG_P3[] = "\"}],\"isError\":false}}";
-
-extern "C" __global__ void __launch_bounds__(WG_DEC_WAVES * WAVE) k_pb2json_wg(
-    const uint8_t* __restrict__ resp_bytes,
-    const uint32_t* __restrict__ resp_off,
-    const int32_t* __restrict__ msg_idx_arr,
-    const uint8_t* __restrict__ id_slots,
-    const SlotResult* __restrict__ enc_results, uint8_t* __restrict__ scratch,
-    const uint32_t* __restrict__ scratch_off, uint8_t* __restrict__ final_out,
-    const uint32_t* __restrict__ final_off, DecodeResult* __restrict__ results,
-    const int32_t* __restrict__ skip, Tables t, int n_req, int max_phase) {
-  // max_phase: debug bisection knob (GGRMCP_WG_PHASES; 3 = full pipeline)
-  int req = blockIdx.x;
-  if (req >= n_req) return;
-  if (!skip || skip[req] != 2) return;  // 2 = routed to this kernel
-
-  // items = top-level field runs; slices = fixed-size spans of the items'
-  // produced text, so the escape passes load-balance across waves even
-  // when one map/array run carries most of the payload
-  constexpr int MAX_SLICES = 1024;
-  __shared__ uint32_t s_start[WG_DEC_MAX_ITEMS + 1];
-  __shared__ uint32_t s_outlen[WG_DEC_MAX_ITEMS];
-  // map / repeated runs are CHUNKED at entry boundaries so one big run
-  // doesn't serialize on a single wave; each chunk's walk emits the full
-  // `"name":{...}` / `"name":[...]` syntax and the joiner trims
-  // s_head bytes of leading name syntax and s_tail closing brackets
-  __shared__ uint16_t s_head[WG_DEC_MAX_ITEMS];
-  __shared__ uint8_t s_tail[WG_DEC_MAX_ITEMS];
-  __shared__ uint16_t s_sl_item[MAX_SLICES];
-  __shared__ uint32_t s_sl_off[MAX_SLICES];   // offset within the item text
-  __shared__ uint32_t s_sl_esc[MAX_SLICES];   // escaped length of the slice
-  __shared__ uint32_t s_sl_fin[MAX_SLICES];   // final-buffer offset
-  __shared__ uint8_t s_sl_comma[MAX_SLICES];  // prepend ',' (item starts)
-  __shared__ int s_nitems, s_nslices, s_next, s_err, s_mode;
-  __shared__ uint32_t s_total, s_slice_bytes;
-
-  const uint8_t* pb = resp_bytes + resp_off[req];
-  const uint32_t wire_len = resp_off[req + 1] - resp_off[req];
-  uint8_t* scr = scratch + scratch_off[req];
-  const uint32_t scr_cap = scratch_off[req + 1] - scratch_off[req];
-  uint8_t* fout = final_out + final_off[req];
-  const uint32_t fcap = final_off[req + 1] - final_off[req];
-  const int lane = lane_id();
-  const int wave = threadIdx.x / WAVE;
-  const int msg_idx = msg_idx_arr[req];
-
-  // ---- phase A: top-level field-run scan (one thread) ---------------------
-  // Runs group contiguous same-number tags; MAP / REPEATED runs split into
-  // ~4 KB chunks at entry boundaries (chunk walks re-emit the name syntax;
-  // s_head/s_tail trim it at join time) so a payload-dominating map field
-  // parallelizes across waves instead of serializing on one.
-  if (threadIdx.x == 0) {
-    s_next = 0;
-    s_err = E_OK;
-    s_mode = 1;
-    int n = 0;
-    uint32_t pos = 0, prev_num = 0, cur = 0xFFFFFFFFu;
-    uint32_t chunk_head = 0;   // head trim for continuation chunks of cur
-    bool cur_split = false;    // cur run may chunk at entry boundaries
-    uint32_t chunk_wire = 0;   // wire bytes accumulated in the open chunk
-    const MsgEntry& tm = t.msgs[msg_idx];
-    bool ok = tm.wkt_kind == WKT_NONE;
-    while (ok && pos < wire_len) {
-      uint32_t tag_start = pos;
-      uint64_t tag;
-      if (!get_varint(pb, wire_len, &pos, &tag)) { ok = false; break; }
-      uint32_t num = (uint32_t)(tag >> 3), wt = (uint32_t)(tag & 7);
-      if (num == 0) { ok = false; break; }
-      if (num != cur) {
-        // close the previous run: its last chunk keeps the bracket
-        if (n > 0) s_tail[n - 1] = 0;
-        // new run must be strictly ascending (non-adjacent duplicates are
-        // the classic path's E_UNSUPPORTED -> host fallback)
-        if (num < prev_num || n >= WG_DEC_MAX_ITEMS) { ok = false; break; }
-        // field lookup decides chunkability (maps + per-entry repeated)
-        cur_split = false;
-        chunk_head = 0;
-        for (int fi = 0; fi < tm.field_count; ++fi) {
-          const FieldEntry& fe = t.fields[tm.field_start + fi];
-          if (fe.number != num) continue;
-          bool per_entry_len =
-              (fe.flags & F_MAP) ||
-              ((fe.flags & F_REPEATED) &&
-               (fe.kind == K_MESSAGE || fe.kind == K_STRING ||
-                fe.kind == K_BYTES));
-          // unpacked repeated scalars (wt != W_LEN run) also chunk
-          bool per_entry_scalar =
-              (fe.flags & F_REPEATED) && !(fe.flags & F_MAP) && wt != W_LEN;
-          if (per_entry_len || per_entry_scalar) {
-            cur_split = true;
-            // `"name":{` / `"name":[` = 1 + json_len + 2 + 1 bytes
-            chunk_head = (uint32_t)fe.json_len + 4;
-          }
-          break;
-        }
-        s_head[n] = 0;
-        s_tail[n] = (uint8_t)(cur_split ? 1 : 0);
-        s_start[n++] = tag_start;
-        prev_num = num;
-        cur = num;
-        chunk_wire = 0;
-      } else if (cur_split && chunk_wire >= 4096) {
-        // continuation chunk of the same run at an entry boundary
-        if (n >= WG_DEC_MAX_ITEMS) { ok = false; break; }
-        s_head[n] = (uint16_t)chunk_head;
-        s_tail[n] = 1;
-        s_start[n++] = tag_start;
-        chunk_wire = 0;
-      }
-      if (wt == W_VARINT) {
-        uint64_t v;
-        if (!get_varint(pb, wire_len, &pos, &v)) { ok = false; break; }
-      } else if (wt == W_I64) {
-        if (pos + 8 > wire_len) { ok = false; break; }
-        pos += 8;
-      } else if (wt == W_I32) {
-        if (pos + 4 > wire_len) { ok = false; break; }
-        pos += 4;
-      } else if (wt == W_LEN) {
-        uint64_t v;
-        if (!get_varint(pb, wire_len, &pos, &v)) { ok = false; break; }
-        if (v > wire_len - pos) { ok = false; break; }
-        pos += (uint32_t)v;
-      } else {
-        ok = false;
-        break;
-      }
-      chunk_wire += pos - tag_start;
-    }
-    if (ok && pos == wire_len && n > 0) {
-      s_tail[n - 1] = 0;  // the wire's last chunk keeps its bracket
-      s_start[n] = wire_len;
-      s_nitems = n;
-    } else {
-      s_mode = 0;  // classic single-wave fallback below
-      s_nitems = 0;
-    }
-  }
-  __syncthreads();
-  const int n_items = s_nitems;
-
-  // ---- phase B: decode items (dynamic wave grabs; the guard bound makes
-  // the loop provably finite — a wave can win at most n_items grabs) ------
-  if (s_mode && max_phase >= 1) {
-    for (int guard = 0; guard <= WG_DEC_MAX_ITEMS + 1; ++guard) {
-      int idx = 0;
-      if (!lane) idx = atomicAdd(&s_next, 1);
-      idx = __shfl(idx, 0, WAVE);
-      if (idx >= n_items) break;
-      uint32_t ist = s_start[idx], ien = s_start[idx + 1];
-      uint32_t soff = 8u * ist + WG_DEC_ITEM_PAD * (uint32_t)idx;
-      uint32_t scap = 8u * (ien - ist) + WG_DEC_ITEM_PAD;
-      if (soff + scap > scr_cap) {
-        if (!lane) {
-          atomicCAS(&s_err, E_OK, E_OVERFLOW);
-          s_outlen[idx] = 0;
-        }
-        continue;
-      }
-      DCtx c;
-      c.pb = pb;
-      c.len = ien;
-      c.pos = ist;
-      c.out = scr + soff;
-      c.opos = 0;
-      c.ocap = scap;
-      c.t = t;
-      c.status = E_OK;
-      c.lane = lane;
-      bool ok = decode_walk(c, msg_idx, ien, /*bare_top=*/true);
-      uint32_t trim = (uint32_t)s_head[idx] + s_tail[idx];
-      if (!ok || c.status != E_OK || c.opos < trim) {
-        if (!lane) {
-          atomicCAS(&s_err, E_OK, c.status == E_OK ? E_PARSE : c.status);
-          s_outlen[idx] = 0;
-        }
-        continue;
-      }
-      // store the TRIMMED length (chunk joins drop re-emitted name syntax
-      // and the premature closing bracket); src offsets add s_head later
-      if (!lane) s_outlen[idx] = c.opos - trim;
-    }
-  }
-  __syncthreads();
-
-  // ---- phase C1: slice the item texts (one thread) ------------------------
-  if (s_mode && threadIdx.x == 0) {
-    s_next = 0;  // re-used by phase C2's grab loop
-    int ns = 0;
-    if (s_err == E_OK) {
-      uint32_t sum = 0;
-      for (int i = 0; i < n_items; ++i) sum += s_outlen[i];
-      uint32_t sb = 4096;
-      uint32_t budget = (uint32_t)(MAX_SLICES - n_items);
-      if (budget > 0 && sum / budget + 1 > sb) sb = sum / budget + 1;
-      s_slice_bytes = sb;
-      bool clipped = false;
-      for (int i = 0; i < n_items && !clipped; ++i) {
-        for (uint32_t off = 0; off < s_outlen[i]; off += sb) {
-          if (ns >= MAX_SLICES) {  // unreachable by the budget math above,
-            clipped = true;        // but NEVER truncate output silently
-            break;
-          }
-          s_sl_item[ns] = (uint16_t)i;
-          s_sl_off[ns] = off;
-          ++ns;
-        }
-      }
-      if (clipped) s_err = E_OVERFLOW;
-    }
-    s_nslices = ns;
-  }
-  __syncthreads();
-  const int n_slices = s_nslices;
-
-  // ---- phase C2: escaped length per slice (wave-parallel) -----------------
-  // static wave-strided assignment: slices are uniform-size, so dynamic
-  // grabbing buys nothing over round-robin
-  if (s_mode && s_err == E_OK && max_phase >= 2) {
-    for (int s = wave; s < n_slices; s += WG_DEC_WAVES) {
-      int item = s_sl_item[s];
-      uint32_t ioff = s_sl_off[s];
-      uint32_t ilen = s_outlen[item] - ioff;
-      if (ilen > s_slice_bytes) ilen = s_slice_bytes;
-      const uint8_t* src = scr + 8u * s_start[item] +
-                           WG_DEC_ITEM_PAD * (uint32_t)item + s_head[item] +
-                           ioff;
-      uint32_t acc = 0;
-      for (uint32_t i = lane; i < ilen; i += WAVE) acc += esc_len(src[i]);
-      for (int d = WAVE / 2; d > 0; d >>= 1) acc += __shfl_down(acc, d, WAVE);
-      if (!lane) s_sl_esc[s] = acc;
-    }
-  }
-  __syncthreads();
-
-  // ---- phase C3: prefix sums + envelope sizing (one thread) ---------------
-  if (s_mode && threadIdx.x == 0) {
-    s_next = 0;  // re-used by phase D's grab loop
-    if (s_err == E_OK) {
-      uint32_t idl = enc_results ? enc_results[req].id_len : 0;
-      uint32_t pre = (uint32_t)(sizeof(WG_P1) - 1) + (idl ? idl : 4) +
-                     (uint32_t)(sizeof(WG_P2) - 1) + 1 /* '{' */;
-      uint32_t off = pre;
-      int first = 1;
-      for (int s = 0; s < n_slices; ++s) {
-        uint8_t comma = 0;
-        if (s_sl_off[s] == 0) {  // first slice of its item
-          if (!first) comma = 1;
-          first = 0;
-        }
-        s_sl_comma[s] = comma;
-        off += comma;
-        s_sl_fin[s] = off;
-        off += s_sl_esc[s];
-      }
-      uint32_t total = off + 1 /* '}' */ + (uint32_t)(sizeof(WG_P3) - 1);
-      if (total > fcap) s_err = E_OVERFLOW;
-      s_total = total;
-    }
-  }
-  __syncthreads();
-
-  // ---- phase D: envelope framing (wave 0) + item escapes (all waves) ------
-  if (s_mode && s_err == E_OK && max_phase >= 3) {
-    if (wave == 0) {
-      DCtx o;
-      o.pb = nullptr;
-      o.len = 0;
-      o.pos = 0;
-      o.out = fout;
-      o.opos = 0;
-      o.ocap = fcap;
-      o.t = t;
-      o.status = E_OK;
-      o.lane = lane;
-      bool ok = puts_(o, WG_P1, sizeof(WG_P1) - 1);
-      uint32_t idl = enc_results ? enc_results[req].id_len : 0;
-      if (ok && idl) {
-        const uint8_t* idp = id_slots + (size_t)req * ID_SLOT_BYTES;
-        for (uint32_t i = lane; i < idl; i += WAVE) o.out[o.opos + i] = idp[i];
-        o.opos += idl;
-      } else if (ok) {
-        ok = puts_(o, "null", 4);
-      }
-      if (ok) ok = puts_(o, WG_P2, sizeof(WG_P2) - 1);
-      if (ok) ok = putc_(o, '{');
-      // closing '}' + P3 at the precomputed end
-      uint32_t cpos = s_total - (uint32_t)(sizeof(WG_P3) - 1) - 1;
-      if (!lane) fout[cpos] = '}';
-      for (uint32_t i = lane; i < sizeof(WG_P3) - 1; i += WAVE)
-        fout[cpos + 1 + i] = (uint8_t)WG_P3[i];
-      if (!ok && !lane) atomicCAS(&s_err, E_OK, o.status);
-    }
-    for (int s = wave; s < n_slices; s += WG_DEC_WAVES) {
-      int item = s_sl_item[s];
-      uint32_t ioff = s_sl_off[s];
-      uint32_t ilen = s_outlen[item] - ioff;
-      if (ilen > s_slice_bytes) ilen = s_slice_bytes;
-      const uint8_t* src = scr + 8u * s_start[item] +
-                           WG_DEC_ITEM_PAD * (uint32_t)item + s_head[item] +
-                           ioff;
-      if (s_sl_comma[s] && !lane) fout[s_sl_fin[s] - 1] = ',';
-      DCtx e;
-      e.pb = nullptr;
-      e.len = 0;
-      e.pos = 0;
-      e.out = fout + s_sl_fin[s];
-      e.opos = 0;
-      e.ocap = s_sl_esc[s];
-      e.t = t;
-      e.status = E_OK;
-      e.lane = lane;
-      // slice of already-validated walker output: skip the UTF-8 re-check
-      // (a boundary can split a multi-byte char; escaping is per-byte)
-      if (!put_escaped(e, src, ilen, /*validate=*/false)) {
-        if (!lane) atomicCAS(&s_err, E_OK, e.status);
-      }
-    }
-  } else if (!s_mode && wave == 0) {
-    // ---- classic single-wave fallback (exact k_pb2json mode-0 body) ------
-    DecodeResult r;
-    r.status = E_OK;
-    r.out_off = final_off[req];
-    r.out_len = 0;
-    r.pad = 0;
-    DCtx c;
-    c.pb = pb;
-    c.len = wire_len;
-    c.pos = 0;
-    c.out = scr;
-    c.opos = 0;
-    c.ocap = scr_cap;
-    c.t = t;
-    c.status = E_OK;
-    c.lane = lane;
-    decode_walk(c, msg_idx, c.len);
-    if (c.status != E_OK) {
-      r.status = c.status;
-      if (!lane) results[req] = r;
-    } else {
-      uint32_t json_len = c.opos;
-      DCtx o;
-      o.pb = nullptr;
-      o.len = 0;
-      o.pos = 0;
-      o.out = fout;
-      o.opos = 0;
-      o.ocap = fcap;
-      o.t = t;
-      o.status = E_OK;
-      o.lane = lane;
-      bool ok = puts_(o, WG_P1, sizeof(WG_P1) - 1);
-      uint32_t idl = enc_results ? enc_results[req].id_len : 0;
-      if (ok && idl) {
-        const uint8_t* idp = id_slots + (size_t)req * ID_SLOT_BYTES;
-        for (uint32_t i = lane; i < idl; i += WAVE) o.out[o.opos + i] = idp[i];
-        o.opos += idl;
-      } else if (ok) {
-        ok = puts_(o, "null", 4);
-      }
-      if (ok) ok = puts_(o, WG_P2, sizeof(WG_P2) - 1);
-      if (ok) ok = put_escaped(o, scr, json_len);
-      if (ok) ok = puts_(o, WG_P3, sizeof(WG_P3) - 1);
-      if (!ok) {
-        r.status = o.status;
-      } else {
-        r.status = E_OK;
-        r.out_len = o.opos;
-      }
-      if (!lane) results[req] = r;
-    }
-  }
-  __syncthreads();
-
-  // ---- finalize (item mode) ------------------------------------------------
-  if (s_mode && threadIdx.x == 0) {
-    DecodeResult r;
-    r.out_off = final_off[req];
-    r.pad = 0;
-    r.status = s_err;
-    r.out_len = s_err == E_OK ? s_total : 0;
-    results[req] = r;
-  }
-}
-#endif  // GGRMCP_HOST_SIM
+// the workgroup-per-request decode kernel and its CPU-build driver
+#include "pb2json_wg.h"

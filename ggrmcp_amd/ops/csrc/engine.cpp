@@ -376,17 +376,18 @@ class Engine : public spanapi::ISpanExecutor {
     h_off_ = {h_ctrl_.p, offs * 3};
     h_aux_ = {(uint8_t*)h_ctrl_.p + ctrl_aux_off_, aux_bytes};
     // results | ids | pb wire in ONE allocation each side: encode returns
-    // everything in ONE D2H span (ids sit right after the USED results at
-    // rid_off_, set per encode; pb at the fixed rid_cap_ — the dead gap
-    // it spans is bandwidth, not an extra submission)
+    // everything in ONE D2H span with no dead gap in it (ids sit right after
+    // the USED results at rid_off_, pb right after the USED ids at pb_base_;
+    // both set per encode, and at most res_cap / rid_cap_)
     size_t res_cap = align64((size_t)max_batch * sizeof(SlotResult));
     size_t id_cap = (size_t)max_batch * ID_SLOT_BYTES;
     rid_off_ = res_cap;
     rid_cap_ = align64(res_cap + id_cap);
+    pb_base_ = rid_cap_;
     d_rid_.alloc(rid_cap_ + cap_pb);
     d_results_ = {d_rid_.p, (size_t)max_batch * sizeof(SlotResult)};
     d_id_slots_ = {(uint8_t*)d_rid_.p + rid_off_, id_cap};
-    d_pb_ = {(uint8_t*)d_rid_.p + rid_cap_, cap_pb};
+    d_pb_ = {(uint8_t*)d_rid_.p + pb_base_, cap_pb};
     d_dec_results_.alloc((size_t)max_batch * sizeof(DecodeResult));
 
     h_in_.alloc(cap_in);
@@ -398,7 +399,13 @@ class Engine : public spanapi::ISpanExecutor {
     h_rid_.alloc(rid_cap_ + cap_pb);
     h_results_ = {h_rid_.p, (size_t)max_batch * sizeof(SlotResult)};
     h_id_ = {(uint8_t*)h_rid_.p + rid_off_, id_cap};
-    h_pb_ = {(uint8_t*)h_rid_.p + rid_cap_, cap_pb};
+    h_pb_ = {(uint8_t*)h_rid_.p + pb_base_, cap_pb};
+    // k_pack_out WRITES the decode results and the packed output bytes
+    // straight into pinned host memory through these device pointers.  As
+    // with the control block, the host keeps off both while a batch is in
+    // flight, and reads them only after the sync_stream() behind the kernel.
+    HIP_CHECK(hipHostGetDevicePointer(&h_rid_dev_, h_rid_.p, 0));
+    HIP_CHECK(hipHostGetDevicePointer(&h_dec_results_dev_, h_dec_results_.p, 0));
   }
 
   ~Engine() {
@@ -921,6 +928,9 @@ class Engine : public spanapi::ISpanExecutor {
   int max_batch() const { return max_batch_; }
   // cumulative count of slots routed to k_pb2json_wg (+= n_wg per batch)
   uint64_t wg_decode_slots() const { return wg_decode_slots_; }
+  // whether the last decode's bytes came packed from k_pack_out (false: the
+  // packed total exceeded cap_pb and the whole final arena was copied)
+  bool compact_used() const { return compact_used_; }
 
  private:
   // JSON-RPC id token of a slot (raw JSON captured by the encode kernel;
@@ -1090,10 +1100,14 @@ class Engine : public spanapi::ISpanExecutor {
         n_wg += esk[i] ? 1 : 0;
       }
     }
-    // pack ids right after the USED results span: one D2H returns both
+    // pack ids right after the USED results span and the pb wire right
+    // after the USED ids: one D2H returns all three and moves live bytes only
     rid_off_ = align64((size_t)n * sizeof(SlotResult));
     d_id_slots_.p = (uint8_t*)d_rid_.p + rid_off_;
     h_id_.p = (uint8_t*)h_rid_.p + rid_off_;
+    pb_base_ = align64(rid_off_ + (size_t)n * ID_SLOT_BYTES);
+    d_pb_.p = (uint8_t*)d_rid_.p + pb_base_;
+    h_pb_.p = (uint8_t*)h_rid_.p + pb_base_;
     auto g0 = std::chrono::steady_clock::now();
     HIP_CHECK(hipSetDevice(device_));
     // chunked pipeline for big batches (mode 0, no msg_idx): overlap the
@@ -1110,11 +1124,10 @@ class Engine : public spanapi::ISpanExecutor {
                                hipMemcpyHostToDevice, stream_));
       launch_encode(0, n, n, has_idx, mode, n_wg, lim);
       // results + id tokens + pb wire in ONE packed D2H span (ids sit at
-      // rid_off_, pb at the fixed rid_cap_; the gap between used ids and
-      // rid_cap_ is dead bandwidth, far cheaper than a second submission).
-      // The native span's C++ error envelopes need the ids on the host;
-      // mode-0 decode keeps reading the device copies.
-      HIP_CHECK(hipMemcpyAsync(h_rid_.p, d_rid_.p, rid_cap_ + pb_bytes,
+      // rid_off_, pb at pb_base_, back to back).  The native span's C++
+      // error envelopes need the ids on the host; mode-0 decode keeps
+      // reading the device copies.
+      HIP_CHECK(hipMemcpyAsync(h_rid_.p, d_rid_.p, pb_base_ + pb_bytes,
                                hipMemcpyDeviceToHost, stream_));
       sync_stream();
     }
@@ -1247,7 +1260,7 @@ class Engine : public spanapi::ISpanExecutor {
   // Chunked decode (envelope kind with a skip array — the serving/wide
   // shapes): chunk c+1's response H2D on stream2_ overlaps chunk c's
   // kernels on stream_ (see run_encode_chunked).  The caller issues the
-  // compact/D2H tail once, after the last chunk.
+  // pack tail once, after the last chunk.
   void run_decode_chunked(int n, int C, const int* cut, int mode, int n_wg) {
     const uint32_t* h_off = (const uint32_t*)h_off_.p;
     for (int c = 0; c < C; ++c) {
@@ -1289,8 +1302,8 @@ class Engine : public spanapi::ISpanExecutor {
     auto g0 = std::chrono::steady_clock::now();
     HIP_CHECK(hipSetDevice(device_));
     uint32_t* d_off = (uint32_t*)d_off3_.p;
-    // chunked pipeline for big response batches; the compact/D2H tail
-    // below is shared
+    // chunked pipeline for big response batches; the pack tail below is
+    // shared
     int cut[PIPE_MAX_CHUNKS + 1];
     int C = 1;
     if (kind == 0 && has_skip && n >= 2 && pipe_chunks() > 1 &&
@@ -1303,39 +1316,31 @@ class Engine : public spanapi::ISpanExecutor {
                                hipMemcpyHostToDevice, stream_));
       launch_decode(0, n, n, has_skip, mode, n_wg);
     }
-    // Device-side compaction: k_tight_scan rewrites out_off to a packed
-    // layout and k_compact_out gathers the used bytes, all before the
-    // first sync — no host prefix-sum round-trip, no tight-table H2D.
-    uint32_t dst_cap = (uint32_t)std::min(d_pb_.n, h_pb_.n);
+    // Packed tail: k_pack_out finds each slot's packed offset itself and
+    // writes the results (h_dec_results_) and the used bytes (h_pb_, at the
+    // base the last encode left) straight into pinned host memory — no
+    // scan kernel, no D2H submissions, one sync.  d_dec_results_ keeps the
+    // arena offsets.
+    uint32_t dst_cap =
+        (uint32_t)std::min(h_pb_.n, (size_t)0xFFFFFFF0u);  // < a saturated off
     if (n > 0) {
-      hipLaunchKernelGGL(k_tight_scan, dim3(1), dim3(256), 0, stream_,
-                         (DecodeResult*)d_dec_results_.p, n);
-      HIP_CHECK(hipGetLastError());
-      hipLaunchKernelGGL(k_compact_out, dim3(n), dim3(256), 0, stream_,
+      hipLaunchKernelGGL(k_pack_out, dim3(n), dim3(PACK_THREADS), 0, stream_,
                          (const uint8_t*)d_final_.p,
                          (const uint32_t*)d_off + (n + 1),
                          (const DecodeResult*)d_dec_results_.p,
-                         (uint8_t*)d_pb_.p, dst_cap, n);
+                         (uint8_t*)h_rid_dev_ + pb_base_,
+                         (DecodeResult*)h_dec_results_dev_, dst_cap, n);
       HIP_CHECK(hipGetLastError());
     }
-    HIP_CHECK(hipMemcpyAsync(h_dec_results_.p, d_dec_results_.p,
-                             n * sizeof(DecodeResult), hipMemcpyDeviceToHost,
-                             stream_));
     sync_stream();
     DecodeResult* rs = (DecodeResult*)h_dec_results_.p;
-    uint64_t acc =
-        n > 0 ? (uint64_t)rs[n - 1].out_off + ((rs[n - 1].out_len + 3u) & ~3u)
-              : 0;
+    uint64_t acc = pack_total(rs, n);
     if (n > 0 && acc <= dst_cap) {
-      if (acc)
-        HIP_CHECK(hipMemcpyAsync(h_pb_.p, d_pb_.p, acc,
-                                 hipMemcpyDeviceToHost, stream_));
-      sync_stream();
       compact_bytes_ = acc;
       compact_used_ = true;
     } else {
-      // packed total overflows the staging arena (k_compact_out skipped
-      // those writes): restore arena offsets and copy the whole arena
+      // packed total overflows the staging arena (k_pack_out wrote no
+      // bytes): restore arena offsets and copy the whole arena
       const uint32_t* final_off = h_off + (n + 1);
       for (int i = 0; i < n; ++i) rs[i].out_off = final_off[i];
       HIP_CHECK(hipMemcpyAsync(h_final_.p, d_final_.p, final_bytes,
@@ -1402,7 +1407,10 @@ class Engine : public spanapi::ISpanExecutor {
   std::unique_ptr<StagePool> stage_pool_;  // lazy (see stage_copies)
   size_t ctrl_aux_off_ = 0;  // aux2 offset inside the ctrl block
   size_t rid_off_ = 0;       // ids offset inside the rid|pb block (per batch)
-  size_t rid_cap_ = 0;       // pb offset inside the rid|pb block (fixed)
+  size_t rid_cap_ = 0;       // largest pb offset inside the rid|pb block
+  size_t pb_base_ = 0;       // pb offset inside the rid|pb block (per encode)
+  void* h_rid_dev_ = nullptr;          // device pointer of h_rid_
+  void* h_dec_results_dev_ = nullptr;  // device pointer of h_dec_results_
   std::vector<std::string> tool_paths_;
   std::vector<int32_t> tool_out_msg_;
   std::vector<int32_t> tool_backend_;
@@ -1509,5 +1517,6 @@ PYBIND11_MODULE(_jsonproto, m) {
            "(span_api.h); the engine must outlive the frontend")
       .def_property_readonly("device", &Engine::device)
       .def_property_readonly("max_batch", &Engine::max_batch)
-      .def_property_readonly("wg_decode_slots", &Engine::wg_decode_slots);
+      .def_property_readonly("wg_decode_slots", &Engine::wg_decode_slots)
+      .def_property_readonly("compact_used", &Engine::compact_used);
 }

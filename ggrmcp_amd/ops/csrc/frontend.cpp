@@ -242,6 +242,8 @@ class Frontend {
     d["decodeMs"] = ns_dec_us_.load() / 1e3;
     d["encodeGpuMs"] = ns_enc_gpu_us_.load() / 1e3;
     d["decodeGpuMs"] = ns_dec_gpu_us_.load() / 1e3;
+    d["engineWaitUs"] = ns_pick_wait_ns_.load() / 1e3;
+    d["engineFirstBusy"] = ns_pick_busy_.load();
     if (rprof_on_) {
       d["rprofBusyMs"] = rprof_.busy_ns.load() / 1e6;
       d["rprofRecvMs"] = rprof_.recv_ns.load() / 1e6;
@@ -767,6 +769,33 @@ class Frontend {
 
   // ---- workers: one GIL crossing per batch --------------------------------
 
+  // Lock a FREE span engine: once round the ring from the round-robin
+  // start, the first try_lock that succeeds.  There are as many workers as
+  // engines, so every try fails only while something other than the workers
+  // holds engines; then block on the starting one.
+  std::unique_lock<std::mutex> take_engine(size_t* ei) {
+    const size_t n = span_execs_.size();
+    const size_t e0 = span_rr_.fetch_add(1) % n;
+    auto w0 = Clock::now();
+    std::unique_lock<std::mutex> lk;
+    for (size_t k = 0; k < n && !lk.owns_lock(); ++k) {
+      *ei = (e0 + k) % n;
+      lk = std::unique_lock<std::mutex>(*span_mu_[*ei], std::try_to_lock);
+      if (k == 0 && !lk.owns_lock())
+        ns_pick_busy_.fetch_add(1, std::memory_order_relaxed);
+    }
+    if (!lk.owns_lock()) {
+      *ei = e0;
+      lk = std::unique_lock<std::mutex>(*span_mu_[e0]);
+    }
+    ns_pick_wait_ns_.fetch_add(
+        (long)std::chrono::duration_cast<std::chrono::nanoseconds>(
+            Clock::now() - w0)
+            .count(),
+        std::memory_order_relaxed);
+    return lk;
+  }
+
   void worker_loop() {
     while (true) {
       std::vector<PendingReq> batch;
@@ -864,10 +893,10 @@ class Frontend {
                               span_enforce_};
           spanapi::SpanOut sout;
           std::string serr;
-          size_t ei = span_rr_.fetch_add(1) % span_execs_.size();
           bool okrun;
           {
-            std::lock_guard<std::mutex> lk(*span_mu_[ei]);
+            size_t ei;
+            std::unique_lock<std::mutex> lk = take_engine(&ei);
             okrun = span_execs_[ei]->run_span(sin, &sout, &serr);
             if (okrun) {
               // materialize responses while the executor is held: the blob
@@ -1078,6 +1107,9 @@ class Frontend {
       ns_err_final_{0}, ns_py_slots_{0}, ns_span_fail_{0};
   std::atomic<long> ns_enc_us_{0}, ns_inv_us_{0}, ns_dec_us_{0},
       ns_enc_gpu_us_{0}, ns_dec_gpu_us_{0};
+  // take_engine: time spent acquiring an engine, and how often the
+  // round-robin start was busy
+  std::atomic<long> ns_pick_wait_ns_{0}, ns_pick_busy_{0};
   bool reuse_port_ = false;
   sesstab::SessionTable* sess_table_ = nullptr;
   bool sess_rate_limit_ = true;
@@ -1119,6 +1151,21 @@ class MockSpanExecutor : public spanapi::ISpanExecutor {
                 std::string* err) override {
     using namespace spanapi;
     calls_++;
+    // "__hold__": keep this executor (and the engine lock its caller holds)
+    // busy until release(), 10 s at the most so that a test cannot hang
+    for (size_t i = 0; i < in.n; ++i) {
+      if (std::string(in.bodies[i], in.body_lens[i]).find("__hold__") ==
+          std::string::npos)
+        continue;
+      std::unique_lock<std::mutex> lk(hold_mu_);
+      holding_ = true;
+      hold_cv_.notify_all();
+      hold_cv_.wait_for(lk, std::chrono::seconds(10),
+                        [this] { return released_; });
+      released_ = false;
+      holding_ = false;
+      break;
+    }
     if (fail_next_) {
       fail_next_ = false;
       *err = "mock failure";
@@ -1164,12 +1211,26 @@ class MockSpanExecutor : public spanapi::ISpanExecutor {
     return true;
   }
   void fail_next() { fail_next_ = true; }
-  long calls() const { return calls_; }
+  long calls() const { return calls_.load(); }
+  // wait until a "__hold__" span is parked in run_span; false on timeout
+  bool wait_held(double timeout_s) {
+    std::unique_lock<std::mutex> lk(hold_mu_);
+    return hold_cv_.wait_for(lk, std::chrono::duration<double>(timeout_s),
+                             [this] { return holding_; });
+  }
+  void release() {
+    std::lock_guard<std::mutex> lk(hold_mu_);
+    released_ = true;
+    hold_cv_.notify_all();
+  }
 
  private:
   std::string blob_;
   bool fail_next_ = false;
-  long calls_ = 0;
+  std::atomic<long> calls_{0};
+  std::mutex hold_mu_;
+  std::condition_variable hold_cv_;
+  bool holding_ = false, released_ = false;
 };
 
 // ---------------------------------------------------------------------------
@@ -1405,5 +1466,8 @@ PYBIND11_MODULE(_frontend, m) {
              return (uintptr_t)(spanapi::ISpanExecutor*)&e;
            })
       .def("fail_next", &MockSpanExecutor::fail_next)
-      .def("calls", &MockSpanExecutor::calls);
+      .def("calls", &MockSpanExecutor::calls)
+      .def("wait_held", &MockSpanExecutor::wait_held, py::arg("timeout_s"),
+           py::call_guard<py::gil_scoped_release>())
+      .def("release", &MockSpanExecutor::release);
 }

@@ -197,6 +197,26 @@ PYBIND11_MODULE(_hostsim, m) {
            py::arg("resp_off"), py::arg("scratch_off"), py::arg("final_off"),
            py::arg("msg_idx"), py::arg("skip"), py::arg("mode") = 0);
 
+  // k_pack_out's offset arithmetic (pb2json.hip pack_partial / pack_place,
+  // summed over the kernel's 256 thread indices) for a batch of out_len
+  // values: (out_off[n], write[n], total) where total is what the engine
+  // reads back, out_off + aligned out_len of the last slot, and the packed
+  // block is used when total <= dst_cap
+  m.def("pack_offsets", [](py::array_t<uint32_t> lens, uint32_t dst_cap) {
+    int n = (int)lens.size();
+    std::vector<DecodeResult> rs(n), packed(n);
+    for (int i = 0; i < n; ++i) rs[i] = {E_OK, 0, lens.data()[i], 0};
+    py::array_t<uint32_t> offs(n);
+    py::array_t<bool> writes(n);
+    for (int i = 0; i < n; ++i) {
+      PackPlace p = pack_slot_host(rs.data(), n, i, dst_cap);
+      packed[i] = rs[i];
+      packed[i].out_off = offs.mutable_data()[i] = p.out_off;
+      writes.mutable_data()[i] = p.write;
+    }
+    return py::make_tuple(offs, writes, pack_total(packed.data(), n));
+  }, py::arg("lens"), py::arg("dst_cap"));
+
   // the native spans' pure host pieces (span_host.h), for the CPU tier
   m.def("grpc_reply", [](int status, const std::string& data,
                          const std::string& msg) {

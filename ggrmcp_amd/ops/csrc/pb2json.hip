@@ -1938,27 +1938,64 @@ extern "C" __global__ void __launch_bounds__(WPB * WAVE) k_pb2json(
   }
 }
 
-// Gather each slot's produced bytes into a tight, contiguous output buffer
-// so the D2H copy moves only used bytes (the final arena is provisioned for
-// worst-case 16x expansion; copying its full capacity back dominated decode
-// time for large payloads: 268 MB vs ~25 MB used at 256 x 64 KB).
-extern "C" __global__ void k_compact_out(
-    const uint8_t* __restrict__ src, const uint32_t* __restrict__ src_off,
-    const DecodeResult* __restrict__ results, uint8_t* __restrict__ dst,
-    uint32_t dst_cap, int n_req) {
-  // destination offsets come from results[].out_off, which k_tight_scan
-  // rewrote to the packed layout; dst_cap guards the (rare) case where
-  // the packed total exceeds the staging arena — the host then takes the
-  // arena-copy fallback and this kernel must not write out of bounds
-  int req = blockIdx.x;
-  if (req >= n_req) return;
-  uint32_t len = results[req].out_len;
-  uint32_t doff = results[req].out_off;
-  if (doff + len > dst_cap || doff + len < doff) return;
-  const uint8_t* s = src + src_off[req];
-  uint8_t* d = dst + doff;
-  uint32_t t = threadIdx.x, stride = blockDim.x;
-  // dword-wide main copy (both offsets 4-aligned by construction)
+// ---- packed output: k_pack_out ----------------------------------------------
+// Each slot's produced bytes go from the final arena (provisioned for
+// worst-case 16x expansion) into a tight block, 4-aligned and in slot order,
+// so that only used bytes reach the host.  The block and the per-slot results
+// are written by the kernel itself, straight into pinned host memory: the
+// host needs no byte count before it can size a copy, so a batch's tail is
+// this one kernel and one sync.
+
+#define PACK_THREADS 256
+
+// (also for the host, which adds the last slot's to its offset: pack_total)
+__host__ DEV uint64_t pack_align4(uint32_t len) {
+  return ((uint64_t)len + 3u) & ~3ull;
+}
+
+// Thread t of `stride`: its share of the aligned out_len sums, over the
+// slots before `req` and over all n.  64-bit, so neither wraps
+// (n <= 4096 lengths below 2^32).
+DEV void pack_partial(const DecodeResult* rs, int n, int req, uint32_t t,
+                      uint32_t stride, uint64_t* before, uint64_t* total) {
+  uint64_t b = 0, a = 0;
+  for (uint32_t j = t; j < (uint32_t)n; j += stride) {
+    uint64_t len4 = pack_align4(rs[j].out_len);
+    a += len4;
+    if (j < (uint32_t)req) b += len4;
+  }
+  *before = b;
+  *total = a;
+}
+
+struct PackPlace {
+  uint32_t out_off;  // packed offset; 0xFFFFFFFF when it does not fit 32 bits
+  bool write;        // the slot's bytes go to the packed block
+};
+
+// Where a slot lands, given the sums over all threads.  No slot writes once
+// the batch total exceeds dst_cap: the host then reads out_off + aligned
+// out_len of the last slot, sees more than dst_cap (the saturated offset
+// keeps a total past 2^32 from looking small) and copies the arena.
+DEV PackPlace pack_place(uint64_t before, uint64_t total, uint32_t len,
+                         uint32_t dst_cap) {
+  PackPlace p;
+  p.out_off = before > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)before;
+  p.write = total <= (uint64_t)dst_cap && before + len <= (uint64_t)dst_cap;
+  return p;
+}
+
+// The batch total as the host reads it back from the packed results; the
+// packed block holds the batch when this is at most dst_cap.
+inline uint64_t pack_total(const DecodeResult* packed, int n) {
+  return n > 0 ? (uint64_t)packed[n - 1].out_off +
+                     pack_align4(packed[n - 1].out_len)
+               : 0;
+}
+
+// dword-wide main copy (both offsets 4-aligned by construction) + byte tail
+DEV void pack_copy(const uint8_t* s, uint8_t* d, uint32_t len, uint32_t t,
+                   uint32_t stride) {
   uint32_t words = len >> 2;
   const uint32_t* s4 = (const uint32_t*)s;
   uint32_t* d4 = (uint32_t*)d;
@@ -1967,37 +2004,66 @@ extern "C" __global__ void k_compact_out(
 }
 
 #ifndef GGRMCP_HOST_SIM
-// Rewrites results[].out_off from arena offsets to a PACKED (4-aligned)
-// layout entirely on device, so the host never round-trips between the
-// decode kernels and k_compact_out (the old flow synced, prefix-summed
-// out_lens on the host, and uploaded a tight-offset table — one extra
-// blocking sync + one extra H2D per batch; the copy-op count is the
-// engine-aggregate ceiling, profiles/contention_r02.md).  One block;
-// contiguous per-thread chunks then a Hillis-Steele scan of the 256
-// partials in LDS.  The packed total lands in rs[n-1] (host recomputes
-// it from out_off + out_len); if it exceeds the arena the host restores
-// arena offsets from final_off and takes the fallback copy.
-extern "C" __global__ void __launch_bounds__(256) k_tight_scan(
-    DecodeResult* __restrict__ rs, int n) {
-  __shared__ uint32_t partial[256];
-  int t = threadIdx.x;
-  int per = (n + 255) / 256;
-  int lo = t * per, hi = n < lo + per ? n : lo + per;
-  uint32_t sum = 0;
-  for (int i = lo; i < hi; ++i) sum += (rs[i].out_len + 3u) & ~3u;
-  partial[t] = sum;
+// One block per slot.  `results` stays as the decode kernels left it (arena
+// offsets); dst_results[req] is its copy with the packed out_off.  dst and
+// dst_results are device pointers into pinned host memory, which the host
+// reads only after the sync that follows the launch.
+extern "C" __global__ void __launch_bounds__(PACK_THREADS) k_pack_out(
+    const uint8_t* __restrict__ src, const uint32_t* __restrict__ src_off,
+    const DecodeResult* __restrict__ results, uint8_t* __restrict__ dst,
+    DecodeResult* __restrict__ dst_results, uint32_t dst_cap, int n_req) {
+  __shared__ uint64_t s_before[PACK_THREADS];
+  __shared__ uint64_t s_total[PACK_THREADS];
+  int req = blockIdx.x;
+  if (req >= n_req) return;
+  uint32_t t = threadIdx.x;
+  pack_partial(results, n_req, req, t, PACK_THREADS, &s_before[t], &s_total[t]);
   __syncthreads();
-  for (int d = 1; d < 256; d <<= 1) {
-    uint32_t v = (t >= d) ? partial[t - d] : 0;
-    __syncthreads();
-    partial[t] += v;
+  for (uint32_t d = PACK_THREADS / 2; d > 0; d >>= 1) {
+    if (t < d) {
+      s_before[t] += s_before[t + d];
+      s_total[t] += s_total[t + d];
+    }
     __syncthreads();
   }
-  uint32_t acc = (t == 0) ? 0 : partial[t - 1];
-  for (int i = lo; i < hi; ++i) {
-    uint32_t len4 = (rs[i].out_len + 3u) & ~3u;
-    rs[i].out_off = acc;
-    acc += len4;
+  DecodeResult r = results[req];
+  PackPlace p = pack_place(s_before[0], s_total[0], r.out_len, dst_cap);
+  if (t == 0) {
+    r.out_off = p.out_off;
+    dst_results[req] = r;
+  }
+  if (p.write)
+    pack_copy(src + src_off[req], dst + p.out_off, r.out_len, t, PACK_THREADS);
+}
+
+#else  // GGRMCP_HOST_SIM
+
+// The kernel above on the CPU: every thread index in turn, for every slot.
+inline PackPlace pack_slot_host(const DecodeResult* results, int n_req, int req,
+                                uint32_t dst_cap) {
+  uint64_t before = 0, total = 0;
+  for (uint32_t t = 0; t < PACK_THREADS; ++t) {
+    uint64_t b, a;
+    pack_partial(results, n_req, req, t, PACK_THREADS, &b, &a);
+    before += b;
+    total += a;
+  }
+  return pack_place(before, total, results[req].out_len, dst_cap);
+}
+
+inline void pack_out_host(const uint8_t* src, const uint32_t* src_off,
+                          const DecodeResult* results, uint8_t* dst,
+                          DecodeResult* dst_results, uint32_t dst_cap,
+                          int n_req) {
+  for (int req = 0; req < n_req; ++req) {
+    DecodeResult r = results[req];
+    PackPlace p = pack_slot_host(results, n_req, req, dst_cap);
+    r.out_off = p.out_off;
+    dst_results[req] = r;
+    if (!p.write) continue;
+    for (uint32_t t = 0; t < PACK_THREADS; ++t)
+      pack_copy(src + src_off[req], dst + p.out_off, r.out_len, t,
+                PACK_THREADS);
   }
 }
 #endif  // GGRMCP_HOST_SIM

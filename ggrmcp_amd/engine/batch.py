@@ -55,6 +55,9 @@ DM_STRUCTURED = 8
 
 SR_ID_IS_MISSING = 1
 SR_SERVER_STREAMING = 2
+# which pass of k_json2pb_wg answered a routed slot (k_json2pb sets neither)
+SR_WG_ITEMS = 4
+SR_WG_CLASSIC = 8
 
 _STATUS_TO_RPC = {
     E_PARSE: (mcp.PARSE_ERROR, "parse error"),

@@ -67,6 +67,13 @@ F_MAP = 4
 F_HAS_PRESENCE = 8
 F_ONEOF = 16
 
+# FieldEntry.oneof_id is one byte and 255 means "no oneof".  The encode
+# kernels track oneofs 0..63 and hand a member of any later oneof to the host
+# (E_UNSUPPORTED), so every index from ONEOF_ID_MAX up is stored as
+# ONEOF_ID_MAX: still a real oneof, still in the host-escape range.
+ONEOF_ID_NONE = 255
+ONEOF_ID_MAX = 254
+
 # msg wkt kinds (msg_table.wkt_kind)
 WKT_NONE = 0
 WKT_TIMESTAMP = 1
@@ -253,13 +260,13 @@ class TableCompiler:
                     flags |= F_MAP
                 if f.has_presence:
                     flags |= F_HAS_PRESENCE
-                oneof_id = 255
+                oneof_id = ONEOF_ID_NONE
                 if f.containing_oneof is not None and not (
                     len(f.containing_oneof.fields) == 1
                     and f.containing_oneof.name == "_" + f.name
                 ):
                     flags |= F_ONEOF
-                    oneof_id = f.containing_oneof.index
+                    oneof_id = min(f.containing_oneof.index, ONEOF_ID_MAX)
                 sub = -1
                 if f.type == _F.TYPE_MESSAGE:
                     sub = self._add_message(f.message_type)

@@ -117,6 +117,8 @@ enum : uint8_t {
 enum : uint32_t {
   W_VARINT = 0, W_I64 = 1, W_LEN = 2, W_SGROUP = 3, W_EGROUP = 4, W_I32 = 5
 };
+// the last legal field number, 2^29 - 1
+constexpr uint64_t MAX_FIELD_NUMBER = 536870911;
 
 // ---------------------------------------------------------------------------
 // Per-request records (kernel <-> host)
@@ -151,6 +153,11 @@ static_assert(sizeof(SlotResult) == 32, "SlotResult layout");
 enum : uint32_t {
   SR_ID_IS_MISSING = 1,   // request had no "id" member
   SR_SERVER_STREAMING = 2,
+  // which encode pass answered a slot routed to k_json2pb_wg (k_json2pb sets
+  // neither): its items (scan + per-item walks, also an envelope it answers
+  // without a walk), or its in-block classic pass
+  SR_WG_ITEMS = 4,
+  SR_WG_CLASSIC = 8,
 };
 
 // result of the decode (respond) kernel, one per request slot

@@ -1151,9 +1151,15 @@ enum : uint8_t {
   RL_SEP = 9,     // EM_LIST: after an element
 };
 
+// Duplicate-member and oneof tracking is exact for field index <
+// SEEN_FIELD_BITS and oneof index < SEEN_ONEOF_BITS; a member beyond either
+// limit leaves with E_UNSUPPORTED (host-escape rule in docs/KERNELS.md).
+constexpr int SEEN_FIELD_BITS = 128;
+constexpr int SEEN_ONEOF_BITS = 64;
+
 struct EFrame {
-  uint64_t seen_fields;
-  uint32_t seen_oneofs;
+  uint64_t seen_fields[2];
+  uint64_t seen_oneofs;
   uint32_t slots[3];   // len slots backfilled (reverse order) on pop
   int32_t msg_idx;
   int32_t cont_field;  // absolute field index of the active array/map
@@ -1541,6 +1547,25 @@ DEVN int encode_msgfield_value(Ctx& c, const FieldEntry& f, uint8_t* push_mode,
   }
 }
 
+// Record member `fidx` (index within its message) in a frame's bit sets.
+// Returns 0 = first occurrence, 1 = duplicate member or second member of a
+// oneof, 2 = beyond SEEN_FIELD_BITS / SEEN_ONEOF_BITS (nothing recorded).
+// No shift count reaches 64.
+DEVN int seen_mark(uint64_t* seen_fields, uint64_t* seen_oneofs, int fidx,
+                   const FieldEntry& fe) {
+  if (fidx >= SEEN_FIELD_BITS) return 2;
+  if ((fe.flags & F_ONEOF) && fe.oneof_id >= SEEN_ONEOF_BITS) return 2;
+  uint64_t bit = 1ull << (fidx & 63);
+  if (seen_fields[fidx >> 6] & bit) return 1;
+  seen_fields[fidx >> 6] |= bit;
+  if (fe.flags & F_ONEOF) {
+    uint64_t ob = 1ull << fe.oneof_id;
+    if (*seen_oneofs & ob) return 1;
+    *seen_oneofs |= ob;
+  }
+  return 0;
+}
+
 // member key lookup inside EM_BODY (hash + dup/oneof bookkeeping);
 // returns field index within the message or -1 (error already set)
 DEVN int encode_body_key(Ctx& c, EFrame& f) {
@@ -1579,19 +1604,13 @@ DEVN int encode_body_key(Ctx& c, EFrame& f) {
     return -1;
   }
   const FieldEntry& fe = c.t.fields[m.field_start + fidx];
-  if (fidx < 64) {
-    if (f.seen_fields & (1ull << fidx)) {
+  int mark = seen_mark(f.seen_fields, &f.seen_oneofs, fidx, fe);
+  if (mark) {
+    if (mark == 2)
+      fail(c, E_UNSUPPORTED);  // beyond the tracked range: host decides
+    else
       fail(c, E_INVALID_PARAMS, (int)fe.number);
-      return -1;
-    }
-    f.seen_fields |= 1ull << fidx;
-  }
-  if (fe.flags & F_ONEOF) {
-    if (f.seen_oneofs & (1u << fe.oneof_id)) {
-      fail(c, E_INVALID_PARAMS, (int)fe.number);
-      return -1;
-    }
-    f.seen_oneofs |= 1u << fe.oneof_id;
+    return -1;
   }
   return m.field_start + fidx;
 }
@@ -1636,7 +1655,7 @@ DEV bool encode_walk(Ctx& c, int top_msg_idx, int wg_item = 0,
   do {                                                        \
     if (sp >= depth_cap) return fail(c, E_LIMIT, 1);          \
     EFrame& nf = stack[sp++];                                 \
-    nf.seen_fields = 0;                                       \
+    nf.seen_fields[0] = nf.seen_fields[1] = 0;                \
     nf.seen_oneofs = 0;                                       \
     nf.msg_idx = (MIDX);                                      \
     nf.cont_field = -1;                                       \
@@ -2393,8 +2412,8 @@ extern "C" __global__ void __launch_bounds__(WG_ENC_WAVES * WAVE) k_json2pb_wg(
       const MsgEntry& m = t.msgs[msg_idx];
       c.pos = args[0];
       c.len = args[1];
-      uint64_t seen = 0;
-      uint32_t seen_oneof = 0;
+      uint64_t seen[2] = {0, 0};
+      uint64_t seen_oneof = 0;
       uint32_t acc = 0;
       bool fallback = m.wkt_kind != WKT_NONE;
       mode_l = 1;
@@ -2432,19 +2451,11 @@ extern "C" __global__ void __launch_bounds__(WG_ENC_WAVES * WAVE) k_json2pb_wg(
               break;
             }
             const FieldEntry& fe = t.fields[m.field_start + fidx];
-            if (fidx < 64) {
-              if (seen & (1ull << fidx)) {
-                fallback = true;  // duplicate member -> classic error
-                break;
-              }
-              seen |= 1ull << fidx;
-            }
-            if (fe.flags & F_ONEOF) {
-              if (seen_oneof & (1u << fe.oneof_id)) {
-                fallback = true;
-                break;
-              }
-              seen_oneof |= 1u << fe.oneof_id;
+            if (seen_mark(seen, &seen_oneof, fidx, fe)) {
+              // duplicate member, second oneof member, or beyond the
+              // tracked range -> classic formats the error
+              fallback = true;
+              break;
             }
             if (!expect(c, ':')) {
               fallback = true;
@@ -2587,8 +2598,8 @@ extern "C" __global__ void __launch_bounds__(WG_ENC_WAVES * WAVE) k_json2pb_wg(
     __shared__ uint32_t mwp1[WG_ENC_MAX_ITEMS], mwp2[MW_D2];
     __shared__ uint32_t s_ob, s_close, s_winb;
     __shared__ int s_nwin, s_cwin, s_fb, s_n1, s_n2;
-    __shared__ unsigned long long s_seenf;
-    __shared__ uint32_t s_seeno;
+    __shared__ unsigned long long s_seenf[2];
+    __shared__ unsigned long long s_seeno;
     __shared__ uint16_t s_mcnt[WG_ENC_MAX_ITEMS];
     __shared__ uint32_t s_mcap[WG_ENC_MAX_ITEMS];
     __shared__ uint32_t s_mbase[WG_ENC_MAX_ITEMS];
@@ -2615,7 +2626,7 @@ extern "C" __global__ void __launch_bounds__(WG_ENC_WAVES * WAVE) k_json2pb_wg(
         s_close = 0;
         s_n1 = 0;
         s_n2 = 0;
-        s_seenf = 0;
+        s_seenf[0] = s_seenf[1] = 0;
         s_seeno = 0;
       }
     }
@@ -2922,13 +2933,17 @@ extern "C" __global__ void __launch_bounds__(WG_ENC_WAVES * WAVE) k_json2pb_wg(
         }
         const FieldEntry& fe = t.fields[mm.field_start + fidx];
         if (!place && !lane) {
-          if (fidx < 64) {
-            unsigned long long bit = 1ull << fidx;
-            if (atomicOr(&s_seenf, bit) & bit) atomicExch(&s_fb, 6);
-          }
-          if (fe.flags & F_ONEOF) {
-            uint32_t b = 1u << fe.oneof_id;
-            if (atomicOr(&s_seeno, b) & b) atomicExch(&s_fb, 6);
+          // same limits as seen_mark(); beyond them classic answers
+          if (fidx >= SEEN_FIELD_BITS ||
+              ((fe.flags & F_ONEOF) && fe.oneof_id >= SEEN_ONEOF_BITS)) {
+            atomicExch(&s_fb, 6);
+          } else {
+            unsigned long long bit = 1ull << (fidx & 63);
+            if (atomicOr(&s_seenf[fidx >> 6], bit) & bit) atomicExch(&s_fb, 6);
+            if (fe.flags & F_ONEOF) {
+              unsigned long long b = 1ull << fe.oneof_id;
+              if (atomicOr(&s_seeno, b) & b) atomicExch(&s_fb, 6);
+            }
           }
         }
         skip_ws(c);
@@ -3129,13 +3144,17 @@ extern "C" __global__ void __launch_bounds__(WG_ENC_WAVES * WAVE) k_json2pb_wg(
     wg_enc_classic_one(src, src_len, pbout, pbcap, results,
                        id_slots + (size_t)req * ID_SLOT_BYTES, keybufs[0], t,
                        lim, req, lane);
-    if (!lane) results[req].pb_off = pb_off[req];
+    if (!lane) {
+      results[req].pb_off = pb_off[req];
+      results[req].flags |= SR_WG_CLASSIC;
+    }
   }
   __syncthreads();
 
   // ---- finalize ------------------------------------------------------------
   if (s_mode != 0 && threadIdx.x == 0) {
     if (s_mode == 1 && max_phase < 2) s_res.pb_len = 0;  // debug phases
+    s_res.flags |= SR_WG_ITEMS;
     results[req] = s_res;
   }
 }

@@ -616,9 +616,12 @@ DEV bool read_varint(DCtx& c, uint64_t* v) {
   return true;
 }
 
-// a field tag: field number 0 is malformed wire (every parser refuses it)
+// a field tag: field number 0 and numbers past 2^29 - 1 (a tag over 32 bits
+// included, whose number would otherwise be cut to 32 bits) are malformed
+// wire; every parser refuses them
 DEV bool read_tag(DCtx& c, uint64_t* tag) {
-  if (!get_varint(c.pb, c.len, &c.pos, tag) || (*tag >> 3) == 0)
+  if (!get_varint(c.pb, c.len, &c.pos, tag) ||
+      (*tag >> 3) - 1 >= MAX_FIELD_NUMBER)
     return dfail(c, E_PARSE);
   return true;
 }

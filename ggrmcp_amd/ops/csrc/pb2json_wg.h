@@ -151,7 +151,7 @@ DEV void wgd_scan(WgDecState& S, const WgDecReq& q, const Tables& t) {
     uint64_t tag;
     if (!get_varint(pb, wire_len, &pos, &tag)) { ok = false; break; }
     uint32_t num = (uint32_t)(tag >> 3), wt = (uint32_t)(tag & 7);
-    if (num == 0) { ok = false; break; }
+    if ((tag >> 3) - 1 >= MAX_FIELD_NUMBER) { ok = false; break; }
     if (num != cur) {
       // close the previous run: its last chunk keeps the bracket
       if (n > 0) S.tail[n - 1] = 0;

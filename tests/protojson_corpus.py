@@ -830,19 +830,33 @@ def _verdict(case: Case, status: int, oracle_ok: bool, equal) -> Optional[str]:
     return f"oracle accepts, kernel status {status}{why}"
 
 
-def run_encode(env: Env, cases: Sequence[Case]) -> dict:
-    """One k_json2pb batch over ``cases``; case id -> None | failure text."""
-    enc, pbs = env.engine.encode_batch(
+def encode_direct(env: Env, cases: Sequence[Case]):
+    """``cases`` as bare JSON (mode 1) through one k_json2pb batch."""
+    return env.engine.encode_batch(
         [c.data.encode() for c in cases], mode=1,
         msg_indices=[env.sink_idx] * len(cases), enforce=False)
-    desc = env.sink_cls.DESCRIPTOR
-    out = {}
-    for c, r, pb in zip(cases, enc, pbs):
-        want = oracle_parse(env.sink_cls, c.data)
 
-        def equal(pb=pb, want=want):
+
+def run_encode(env: Env, cases: Sequence[Case], encode=encode_direct) -> dict:
+    """One encode batch over ``cases``; case id -> None | failure text.
+    ``encode(env, cases)`` returns (slot results, wires): the bare form by
+    default, or any other carrier of the same JSON text (a tools/call
+    envelope, a workgroup-routed batch) judged by the same verdicts."""
+    enc, pbs = encode(env, cases)
+    return encode_verdicts(cases, [env.sink_cls] * len(cases), enc, pbs)
+
+
+def encode_verdicts(cases: Sequence[Case], classes, enc, pbs) -> dict:
+    """The encode contract over one batch's results; ``classes[i]`` is the
+    message class of ``cases[i]``."""
+    out = {}
+    for c, cls, r, pb in zip(cases, classes, enc, pbs):
+        want = oracle_parse(cls, c.data)
+        desc = cls.DESCRIPTOR
+
+        def equal(pb=pb, want=want, cls=cls, desc=desc):
             try:
-                got = env.sink_cls.FromString(pb)
+                got = cls.FromString(pb)
             except Exception as exc:
                 return f"kernel wire does not parse: {exc!r} {pb!r}"
             g = json_format.MessageToDict(got)

@@ -16,6 +16,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 from test_gpu_wg_decode import _body, _first_diff, _shapes, env  # noqa: F401,E402
+from ggrmcp_amd.engine.batch import SR_WG_CLASSIC, SR_WG_ITEMS  # noqa: E402
 
 
 def _enc(pipeline, bodies, mw, wg_min="4096"):
@@ -167,3 +168,15 @@ def test_mw_scan_adversarial_strings(env):  # noqa: F811
     serial = _enc(pipeline, bodies, mw=False, wg_min="2048")
     mw = _enc(pipeline, bodies, mw=True, wg_min="2048")
     _assert_equal(bodies, serial, mw)
+    # and to the classic kernel; none of these has a scanner anomaly, so what
+    # is accepted was answered from the items, and the classic kernel tags no
+    # path
+    classic = _enc(pipeline, bodies, mw=False, wg_min="1000000000")
+    _assert_equal(bodies, classic, mw)
+    paths = SR_WG_ITEMS | SR_WG_CLASSIC
+    for i in range(len(bodies)):
+        for enc in (mw[0], serial[0]):
+            assert enc[i]["flags"] & paths in (SR_WG_ITEMS, SR_WG_CLASSIC), i
+            if enc[i]["status"] == 0:
+                assert enc[i]["flags"] & paths == SR_WG_ITEMS, (i, enc[i]["flags"])
+        assert classic[0][i]["flags"] & paths == 0, (i, classic[0][i]["flags"])

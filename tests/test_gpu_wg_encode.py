@@ -15,6 +15,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 from test_gpu_wg_decode import _body, _first_diff, _shapes, env  # noqa: F401,E402
+from ggrmcp_amd.engine.batch import SR_WG_CLASSIC, SR_WG_ITEMS  # noqa: E402
 
 
 def test_wg_encode_matches_classic_bytes(env):  # noqa: F811
@@ -105,3 +106,8 @@ def test_wg_encode_error_paths(env):  # noqa: F811
             i, enc_a[i]["status"], enc_b[i]["status"])
         assert enc_a[i]["err_pos"] == enc_b[i]["err_pos"], i
         assert enc_a[i]["aux"] == enc_b[i]["aux"], i
+        # both are scanner anomalies: the in-block classic pass answered, and
+        # the classic kernel tags no path
+        assert enc_b[i]["status"] != 0
+        assert enc_b[i]["flags"] & (SR_WG_ITEMS | SR_WG_CLASSIC) == SR_WG_CLASSIC, i
+        assert enc_a[i]["flags"] & (SR_WG_ITEMS | SR_WG_CLASSIC) == 0, i

@@ -77,3 +77,36 @@ def test_oneof_and_map_flags():
     assert flags_by_name["text"] & T.F_ONEOF
     assert flags_by_name["binary"] & T.F_ONEOF
     assert flags_by_name["metadata"] & T.F_MAP
+
+
+def test_oneof_index_never_reads_as_none():
+    """oneof_id is one byte and 255 means "no oneof": a real oneof with index
+    254, 255 or more is stored as ONEOF_ID_MAX (254), which the encode kernels
+    hand to the host like every oneof index from 64 up."""
+    from ggrmcp_amd.utils.protobuild import FileBuilder
+
+    fb = FileBuilder("t/many_oneofs.proto", "t")
+    m = fb.message("Many")
+    for o in range(300):
+        m.field(f"a{o}", 2 * o + 1, "int32", oneof=f"o{o}")
+        m.field(f"b{o}", 2 * o + 2, "string", oneof=f"o{o}")
+    m.field("opt", 601, "int32", optional=True)
+    m.field("plain", 602, "int32")
+    m.done()
+    fb.service("ManyService").method("Echo", "Many", "Many").done()
+    fdps = [fb.build()]
+    pool = build_pool(fdps)
+    infos = extract_method_infos(fdps, pool, compat_names=False)
+    ct = T.compile_tables({mi.tool_name(): mi for mi in infos})
+    start, count, _, _ = struct.unpack_from(
+        T.MSG_ENTRY_FMT, ct.msg_table, ct.msg_index["t.Many"] * T.MSG_ENTRY_SIZE)
+    assert count == 602
+    recs = [struct.unpack_from(T.FIELD_ENTRY_FMT, ct.field_table,
+                               (start + i) * T.FIELD_ENTRY_SIZE)
+            for i in range(count)]
+    assert T.ONEOF_ID_MAX == 254 and T.ONEOF_ID_NONE == 255
+    for i, rec in enumerate(recs[:600]):
+        assert rec[9] & T.F_ONEOF
+        assert rec[10] == min(i // 2, T.ONEOF_ID_MAX), (i, rec[10])
+    for rec in recs[600:]:
+        assert not rec[9] & T.F_ONEOF and rec[10] == T.ONEOF_ID_NONE

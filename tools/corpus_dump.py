@@ -1,5 +1,6 @@
 """Write the protojson corpus (tests/protojson_corpus.py), the Any corpus
-(tests/any_corpus.py) and their compiled tables to one binary file for
+(tests/any_corpus.py), the wide-schema corpus (tests/wide_schema_corpus.py)
+and their compiled tables to one binary file for
 tools/asan_corpus.cpp — the stand-alone sanitizer run of the kernel logic
 (no Python in the sanitized process).
 
@@ -19,6 +20,7 @@ sys.path[:0] = [str(ROOT), str(ROOT / "tests")]
 
 import any_corpus as ac  # noqa: E402
 import protojson_corpus as pc  # noqa: E402
+import wide_schema_corpus as wc  # noqa: E402
 from ggrmcp_amd.engine.tables import compile_tables  # noqa: E402
 
 
@@ -52,6 +54,13 @@ def _any_cases(env):
     return cases
 
 
+def _wide_cases(env):
+    cases = [(0, env.idx[c.msg], c.data.encode())
+             for c in wc.ACCEPT + wc.REJECT + wc.GO_STRICT]
+    cases += [(1, env.idx[c.msg], c.data) for c in wc.wires(env)]
+    return cases
+
+
 def main(out_path: str) -> None:
     env = pc.make_env(_Tables)
     t = env.engine.tables
@@ -67,10 +76,14 @@ def main(out_path: str) -> None:
         cases.append((0, env.inner_idx, b))
     any_env = ac.make_env(_Tables)
     any_cases = _any_cases(any_env)
+    wide_env = wc.make_env(_Tables)
+    wide_cases = _wide_cases(wide_env)
     with open(out_path, "wb") as f:
         _write_section(f, t, cases)
         _write_section(f, any_env.engine.tables, any_cases)
-    print(f"{len(cases)} + {len(any_cases)} Any cases -> {out_path}")
+        _write_section(f, wide_env.engine.tables, wide_cases)
+    print(f"{len(cases)} + {len(any_cases)} Any + {len(wide_cases)} wide-schema "
+          f"cases -> {out_path}")
 
 
 if __name__ == "__main__":

@@ -62,6 +62,12 @@ def parse_args(argv: Optional[List[str]] = None) -> argparse.Namespace:
         help="return MCP structuredContent that satisfies each tool's "
              "outputSchema (unpopulated fields printed)",
     )
+    ap.add_argument(
+        "--reorder-wire",
+        action="store_true",
+        help="transcode responses with out-of-order or re-occurring fields "
+             "on the GPU (canonical re-ordering pass) instead of on the host",
+    )
     return ap.parse_args(argv)
 
 
@@ -95,6 +101,8 @@ def build_config(args: argparse.Namespace) -> Config:
         cfg.gpu.enabled = False
     if getattr(args, "structured_content", False):
         cfg.server.structured_content = True
+    if getattr(args, "reorder_wire", False):
+        cfg.gpu.reorder_wire = True
     cfg.validate()
     return cfg
 

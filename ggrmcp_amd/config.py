@@ -147,6 +147,12 @@ class GPUConfig:
     devices: int = 1  # engines (== visible GPUs) for DP session sharding
     batch_window_us: int = 200  # adaptive batch collection window
     max_batch: int = 4096  # requests per GPU batch
+    # Responses whose fields arrive out of number order, or re-occur, are
+    # put into canonical order on the device (k_pb_reorder) instead of going
+    # to the host transcoder.  Costs one more launch per decode and a device
+    # arena of 3x the response arena, allocated on first use.  Off: today's
+    # launches and bytes.
+    reorder_wire: bool = False
     # Engine instances (each with its own HIP stream + arenas) per device.
     # 2 measured best with the native span executor: overlap pays, but HIP
     # runtime contention grows superlinearly with instance count

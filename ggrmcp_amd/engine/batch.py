@@ -52,6 +52,7 @@ E_NOT_TOOLCALL = 8
 # decode `mode` flag bits above the kind (mode & 3); mirror common.h DM_*
 DM_UNPOPULATED = 4
 DM_STRUCTURED = 8
+DM_REORDER = 16
 
 SR_ID_IS_MISSING = 1
 SR_SERVER_STREAMING = 2
@@ -192,12 +193,28 @@ class GpuEngine:
         self._lock = threading.RLock()
         self.structured_flags = 0
         self.set_structured_content(self.config.server.structured_content)
+        self.reorder_flag = 0
+        self.set_reorder_wire(self.config.gpu.reorder_wire)
 
     def set_structured_content(self, on: bool) -> None:
         """Serving spans print unpopulated fields and carry the object as
         structuredContent too (sizes the final arena for both copies)."""
         self._eng.set_structured_content(bool(on))
         self.structured_flags = (DM_UNPOPULATED | DM_STRUCTURED) if on else 0
+
+    def set_reorder_wire(self, on: bool) -> None:
+        """Serving spans send slots the decode kernels refuse as out of field
+        order through k_pb_reorder (the arena is allocated on first use)."""
+        self._eng.set_reorder_wire(bool(on))
+        self.reorder_flag = DM_REORDER if on else 0
+
+    @property
+    def reorder_slots(self) -> int:
+        """Slots k_pb_reorder has re-ordered and re-decoded, ever
+        (``DecodeResult.pad`` 3).  That includes the few whose canonical wire
+        the re-decode refused too: their status is non-zero and the host
+        still answers them."""
+        return int(self._eng.reorder_slots)
 
     @property
     def wg_decode_slots(self) -> int:
@@ -428,8 +445,9 @@ class GpuPipeline:
                 rpc_error[i] = e
         st.invoke_ns += time.perf_counter_ns() - t0
 
-        dec, finals = engine.decode_batch(resp_wire, out_idx,
-                                          mode=0 | engine.structured_flags)
+        dec, finals = engine.decode_batch(
+            resp_wire, out_idx,
+            mode=0 | engine.structured_flags | engine.reorder_flag)
 
         # streaming: gather chunk lists, decode ALL chunks of ALL streams in
         # one value-mode GPU batch, assemble envelopes host-side
@@ -477,7 +495,8 @@ class GpuPipeline:
         for base in range(0, len(flat), cap):
             with engine._lock:
                 _, part = engine.decode_batch(
-                    flat[base : base + cap], flat_idx[base : base + cap], mode=2
+                    flat[base : base + cap], flat_idx[base : base + cap],
+                    mode=2 | engine.reorder_flag,
                 )
             jsons.extend(part)
         out: Dict[int, bytes] = {}
@@ -928,7 +947,8 @@ class BatchEngineInvoker:
         eng.stats.invoke_ns += time.perf_counter_ns() - t0
         # bare JSON for the handler, which builds structuredContent from it
         dec, jsons = eng.decode_batch(
-            wires, out_idx, mode=1 | (eng.structured_flags & DM_UNPOPULATED))
+            wires, out_idx,
+            mode=1 | (eng.structured_flags & DM_UNPOPULATED) | eng.reorder_flag)
         for i in ok_slots:
             if wires[i] is None:
                 continue

@@ -166,7 +166,8 @@ struct __attribute__((packed)) DecodeResult {
   uint32_t out_off;  // final response bytes in the output arena
   uint32_t out_len;
   // which decode pass answered: 0 = k_pb2json, 1 = k_pb2json_wg's items,
-  // 2 = k_pb2json_wg's in-block classic pass
+  // 2 = k_pb2json_wg's in-block classic pass, 3 = k_pb_reorder (the wire was
+  // rewritten into canonical order first)
   uint32_t pad;
 };
 static_assert(sizeof(DecodeResult) == 16, "DecodeResult layout");
@@ -182,6 +183,9 @@ enum : int {
   // envelope (kind 0) also carries the raw JSON as "structuredContent";
   // needs final_cap + scratch_cap bytes of final arena per slot
   DM_STRUCTURED = 8,
+  // slots the decode kernels leave at E_UNSUPPORTED go through k_pb_reorder:
+  // canonical field order first, then the classic walk (pb_reorder.h)
+  DM_REORDER = 16,
 };
 
 // protojson value ranges of the time WKTs (both directions refuse the rest)
@@ -466,6 +470,13 @@ constexpr uint32_t WG_ENC_MIN_BYTES = 16384;
 constexpr int WG_ENC_MAX_ITEMS = 384;
 constexpr uint32_t WG_ENC_ITEM_PAD = 160;
 constexpr int WG_ENC_WAVES = 16;
+
+// Wire re-ordering (k_pb_reorder, DM_REORDER).  Each cap is a give-up rule:
+// the slot keeps E_UNSUPPORTED and the host answers it.
+constexpr int RO_MAX_RUNS = 256;    // run records of ONE body (the LDS window)
+constexpr int RO_STACK_RUNS = 512;  // sorted records of all open frames, per wave
+constexpr int RO_GRID_BLOCKS = 256; // launch grid cap: the work area is per wave
+constexpr uint32_t RO_SLOT_PAD = 16;  // arena bytes per slot past 3 * wire_len
 
 // u64 -> decimal text without an addressable temp buffer (a local tmp[20]
 // array lands in scratch memory and costs a private-memory round trip per

@@ -908,7 +908,15 @@ class Engine : public spanapi::ISpanExecutor {
   // add structuredContent to every result envelope; their final arena is
   // then sized for both copies of the JSON.  Off by default.
   void set_structured_content(bool on) {
-    span_flags_ = on ? (DM_UNPOPULATED | DM_STRUCTURED) : 0;
+    span_flags_ = (span_flags_ & DM_REORDER) |
+                  (on ? (DM_UNPOPULATED | DM_STRUCTURED) : 0);
+  }
+
+  // Serving spans send the slots the decode kernels refuse as out of field
+  // order through k_pb_reorder (DM_REORDER).  Off by default; the arena is
+  // allocated by the first decode that carries the flag.
+  void set_reorder_wire(bool on) {
+    span_flags_ = (span_flags_ & ~DM_REORDER) | (on ? DM_REORDER : 0);
   }
 
   // (encode_ms, invoke_ms, decode_ms) of the LAST process_span call;
@@ -928,6 +936,8 @@ class Engine : public spanapi::ISpanExecutor {
   int max_batch() const { return max_batch_; }
   // cumulative count of slots routed to k_pb2json_wg (+= n_wg per batch)
   uint64_t wg_decode_slots() const { return wg_decode_slots_; }
+  // cumulative count of slots k_pb_reorder answered (DecodeResult.pad == 3)
+  uint64_t reorder_slots() const { return reorder_slots_; }
   // whether the last decode's bytes came packed from k_pack_out (false: the
   // packed total exceeded cap_pb and the whole final arena was copied)
   bool compact_used() const { return compact_used_; }
@@ -1257,6 +1267,34 @@ class Engine : public spanapi::ISpanExecutor {
     }
   }
 
+  // The reorder arena (canonical wire + side buffer per slot, pb_reorder.h
+  // ro_region) and the record stacks of the waves of one launch grid.
+  // Neither grows with the batch; nothing exists until the flag is first set.
+  void ensure_reorder_arena() {
+    if (d_reorder_.p) return;
+    d_reorder_.alloc(3 * d_resp_.n + (size_t)RO_SLOT_PAD * (size_t)max_batch_);
+    d_ro_work_.alloc((size_t)RO_GRID_BLOCKS * WPB * RO_STACK_RUNS *
+                     sizeof(RoRec));
+  }
+
+  // k_pb_reorder over slots [lo, lo+m) of an n-slot batch, on stream_ behind
+  // the decode kernels of the same slots: the only launch of that kernel.
+  void launch_reorder(int lo, int m, int n, bool has_skip, int mode) {
+    int blocks = (int)std::min<uint64_t>(cdiv(m, WPB), RO_GRID_BLOCKS);
+    if (blocks <= 0) return;
+    const uint32_t* off = (const uint32_t*)d_off3_.p;
+    hipLaunchKernelGGL(
+        k_pb_reorder, dim3(blocks), dim3(WPB * WAVE), 0, stream_,
+        (const uint8_t*)d_resp_.p, off + lo, (const int32_t*)d_aux2_.p + lo,
+        (const uint8_t*)d_id_slots_.p + (size_t)lo * ID_SLOT_BYTES,
+        (mode & DM_KIND) == 0 ? (const SlotResult*)d_results_.p + lo : nullptr,
+        (uint8_t*)d_scratch_.p, off + 2 * (n + 1) + lo, (uint8_t*)d_final_.p,
+        off + (n + 1) + lo, (DecodeResult*)d_dec_results_.p + lo,
+        has_skip ? (const int32_t*)d_aux2_.p + n + lo : nullptr,
+        (uint8_t*)d_reorder_.p, (RoRec*)d_ro_work_.p, tables_, m, mode, lo);
+    HIP_CHECK(hipGetLastError());
+  }
+
   // Chunked decode (envelope kind with a skip array — the serving/wide
   // shapes): chunk c+1's response H2D on stream2_ overlaps chunk c's
   // kernels on stream_ (see run_encode_chunked).  The caller issues the
@@ -1273,6 +1311,7 @@ class Engine : public spanapi::ISpanExecutor {
       HIP_CHECK(hipEventRecord(ev_h2d_[c], stream2_));
       HIP_CHECK(hipStreamWaitEvent(stream_, ev_h2d_[c], 0));
       launch_decode(lo, m, n, true, mode, n_wg);
+      if (mode & DM_REORDER) launch_reorder(lo, m, n, true, mode);
     }
   }
 
@@ -1301,6 +1340,7 @@ class Engine : public spanapi::ISpanExecutor {
     wg_decode_slots_ += (uint64_t)n_wg;
     auto g0 = std::chrono::steady_clock::now();
     HIP_CHECK(hipSetDevice(device_));
+    if (mode & DM_REORDER) ensure_reorder_arena();
     uint32_t* d_off = (uint32_t*)d_off3_.p;
     // chunked pipeline for big response batches; the pack tail below is
     // shared
@@ -1315,6 +1355,7 @@ class Engine : public spanapi::ISpanExecutor {
       HIP_CHECK(hipMemcpyAsync(d_resp_.p, h_resp_.p, resp_bytes,
                                hipMemcpyHostToDevice, stream_));
       launch_decode(0, n, n, has_skip, mode, n_wg);
+      if (mode & DM_REORDER) launch_reorder(0, n, n, has_skip, mode);
     }
     // Packed tail: k_pack_out finds each slot's packed offset itself and
     // writes the results (h_dec_results_) and the used bytes (h_pb_, at the
@@ -1334,6 +1375,8 @@ class Engine : public spanapi::ISpanExecutor {
     }
     sync_stream();
     DecodeResult* rs = (DecodeResult*)h_dec_results_.p;
+    if (mode & DM_REORDER)
+      for (int i = 0; i < n; ++i) reorder_slots_ += rs[i].pad == 3;
     uint64_t acc = pack_total(rs, n);
     if (n > 0 && acc <= dst_cap) {
       compact_bytes_ = acc;
@@ -1384,6 +1427,7 @@ class Engine : public spanapi::ISpanExecutor {
   double last_enc_gpu_ms_ = 0.0, last_dec_gpu_ms_ = 0.0;
   int last_batch_n_ = -1;
   uint64_t wg_decode_slots_ = 0;  // slots routed to k_pb2json_wg, ever
+  uint64_t reorder_slots_ = 0;    // slots answered by k_pb_reorder, ever
   int span_flags_ = 0;  // DM_* flags OR-ed into the serving spans' decode mode
   bool compact_used_ = false;
   size_t compact_bytes_ = 0;
@@ -1400,6 +1444,7 @@ class Engine : public spanapi::ISpanExecutor {
   DeviceBuf d_msgs_, d_fields_, d_enums_, d_enum_vals_, d_tools_, d_names_,
       d_types_;
   DeviceBuf d_in_, d_resp_, d_scratch_, d_final_;
+  DeviceBuf d_reorder_, d_ro_work_;  // lazy (see ensure_reorder_arena)
   DeviceBuf d_rid_, d_dec_results_;
   BufView d_off3_, d_aux2_, d_results_, d_id_slots_, d_pb_;
   PinnedBuf h_in_, h_resp_, h_final_, h_dec_results_, h_ctrl_, h_rid_;
@@ -1509,6 +1554,7 @@ PYBIND11_MODULE(_jsonproto, m) {
            py::arg("msg_idx"), py::arg("skip") = py::none(), py::arg("mode") = 0)
       .def("set_structured_content", &Engine::set_structured_content,
            py::arg("on"))
+      .def("set_reorder_wire", &Engine::set_reorder_wire, py::arg("on"))
       .def("last_stage_ms", &Engine::last_stage_ms)
       .def("last_gpu_ms", &Engine::last_gpu_ms)
       .def("span_handle",
@@ -1518,5 +1564,6 @@ PYBIND11_MODULE(_jsonproto, m) {
       .def_property_readonly("device", &Engine::device)
       .def_property_readonly("max_batch", &Engine::max_batch)
       .def_property_readonly("wg_decode_slots", &Engine::wg_decode_slots)
+      .def_property_readonly("reorder_slots", &Engine::reorder_slots)
       .def_property_readonly("compact_used", &Engine::compact_used);
 }

@@ -134,6 +134,17 @@ class HostEngine {
                      last_ids_.data(), last_results_.data(), scratch.data(),
                      scratch_off.data(), fin.data(), final_off.data(),
                      results.data(), skip_ptr, t_, n, mode);
+    if (mode & DM_REORDER) {
+      // k_pb_reorder's phases over the slots left at E_UNSUPPORTED, in an
+      // arena laid out as the engine's (pb_reorder.h ro_region)
+      std::vector<uint8_t> arena(ro_region(resp_off_v(n), n), 0);
+      reorder_host((const uint8_t*)din.ptr, resp_off.data(), msg_idx.data(),
+                   (mode & DM_KIND) == 0 ? last_ids_.data() : nullptr,
+                   (mode & DM_KIND) == 0 ? last_results_.data() : nullptr,
+                   scratch.data(), scratch_off.data(), fin.data(),
+                   final_off.data(), results.data(), skip_ptr, arena.data(),
+                   t_, n, mode);
+    }
     py::array_t<uint8_t> res({(py::ssize_t)(n * sizeof(DecodeResult))});
     std::memcpy(res.mutable_data(), results.data(), n * sizeof(DecodeResult));
     return py::make_tuple(res, py::bytes((const char*)fin.data(), fin.size()));

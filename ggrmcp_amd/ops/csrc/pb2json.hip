@@ -2073,3 +2073,6 @@ inline void pack_out_host(const uint8_t* src, const uint32_t* src_off,
 
 // the workgroup-per-request decode kernel and its CPU-build driver
 #include "pb2json_wg.h"
+
+// the wire re-ordering pass behind DM_REORDER and its CPU-build driver
+#include "pb_reorder.h"

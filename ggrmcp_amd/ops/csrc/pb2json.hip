@@ -23,7 +23,9 @@
 // the host transcodes that request (counted, never silent).
 // google.protobuf.Any prints on the device when its wire is [type_url]
 // [value] and the URL resolves in the type table (decode_any_head).  Doubles print as 17-significant-digit shortest-trimmed decimals
-// (value-exact round trip; not always the minimal digit string).
+// (value-exact round trip; not always the minimal digit string).  Packed
+// fixed-width runs print one element per lane with exact shortest digits
+// (emit_packed_fixed, fp_shortest.h).
 
 #include "common.h"
 
@@ -38,6 +40,8 @@
 #else
 #define DEVN __device__ __noinline__
 #endif
+
+#include "fp_shortest.h"
 
 #ifndef WPB
 #define WPB 4
@@ -855,8 +859,206 @@ DEVN bool emit_scalar_value(DCtx& c, const FieldEntry& f) {
   return dfail(c, E_UNSUPPORTED);
 }
 
+// ---------------------------------------------------------------------------
+// Packed fixed-width runs (double, float, [s]fixed32, [s]fixed64): one
+// element per lane.  Element i sits at pos + width * i, so no scan is needed
+// to find it; the lane formats its own value into registers (PfText), an
+// inclusive wave scan of the text lengths places it, and the lanes store
+// their bytes straight into the output (docs/KERNELS.md, "Packed fixed-width
+// runs").  At WAVE=1 a window is one element, which is how the CPU build
+// runs this code.
+// ---------------------------------------------------------------------------
+
+enum : uint32_t {
+  PF_INT = 0,   // [-]digits, `quoted` for the 64-bit kinds; also +-0.0
+  PF_FP = 1,    // [-]digits/ndig/e10 in emit_double_body's layout
+  PF_NAN = 2,   // "NaN"
+  PF_INF = 3,   // "Infinity" / "-Infinity"
+};
+
+// what one lane prints; every member lives in a register
+struct PfText {
+  uint64_t digits;  // decimal digits, most significant printed first
+  int32_t ndig;
+  int32_t e10;      // PF_FP: value = d.ddd * 10^e10
+  uint32_t form;
+  bool neg, quoted;
+};
+
+DEV uint32_t pf_count_digits(uint64_t v) {
+  uint32_t n = 1;
+  while (n < 20 && v >= DEC_P10[n]) ++n;
+  return n;
+}
+
+// little-endian element of 4 or 8 bytes at any alignment, in dword pieces
+DEV uint64_t pf_load(const uint8_t* p, bool wide) {
+  uint32_t lo, hi = 0;
+  __builtin_memcpy(&lo, p, 4);
+  if (wide) __builtin_memcpy(&hi, p + 4, 4);
+  return (uint64_t)hi << 32 | lo;
+}
+
+DEV PfText pf_format(uint32_t kind, uint64_t bits) {
+  PfText t;
+  t.digits = 0;
+  t.ndig = 1;
+  t.e10 = 0;
+  t.form = PF_INT;
+  t.neg = false;
+  t.quoted = kind == K_FIXED64 || kind == K_SFIXED64;
+  if (kind == K_DOUBLE || kind == K_FLOAT) {
+    const bool flt = kind == K_FLOAT;
+    const uint64_t sign = flt ? 0x80000000ull : 0x8000000000000000ull;
+    const uint64_t expo = flt ? 0x7f800000ull : 0x7ff0000000000000ull;
+    t.neg = (bits & sign) != 0;
+    bits &= sign - 1;
+    if (bits > expo) {
+      t.form = PF_NAN;
+      t.neg = false;
+    } else if (bits == expo) {
+      t.form = PF_INF;
+    } else if (bits) {
+      FpsDec r = flt ? fps_shortest_float((uint32_t)bits) : fps_shortest_double(bits);
+      t.form = PF_FP;
+      t.digits = r.digits;
+      t.ndig = r.ndig;
+      t.e10 = r.e10;
+    }
+    return t;
+  }
+  if (kind == K_SFIXED32 || kind == K_SFIXED64) {
+    int64_t sv = kind == K_SFIXED32 ? (int64_t)(int32_t)(uint32_t)bits : (int64_t)bits;
+    t.neg = sv < 0;
+    bits = t.neg ? (uint64_t)(~sv) + 1ull : (uint64_t)sv;
+  }
+  t.digits = bits;
+  t.ndig = (int32_t)pf_count_digits(bits);
+  return t;
+}
+
+// text length; at most 25 bytes (-0.000001234567890123456)
+DEV uint32_t pf_len(const PfText& t) {
+  if (t.form == PF_NAN) return 5;
+  if (t.form == PF_INF) return 10 + (t.neg ? 1 : 0);
+  uint32_t n = (t.neg ? 1 : 0) + (uint32_t)t.ndig;
+  if (t.form == PF_INT) return n + (t.quoted ? 2 : 0);
+  if (t.e10 >= -6 && t.e10 <= 20) {
+    if (t.e10 < 0) return n + 1 + (uint32_t)(-t.e10);        // 0.000ddd
+    if (t.ndig > t.e10 + 1) return n + 1;                    // dd.ddd
+    return n + (uint32_t)(t.e10 + 1 - t.ndig);               // ddd000
+  }
+  int e = t.e10 < 0 ? -t.e10 : t.e10;
+  return n + (t.ndig > 1 ? 1 : 0) + 2 + (e >= 100 ? 3 : 2);  // d.ddde+XX
+}
+
+// least significant digit of v, which loses it; 32-bit once v fits
+DEV uint8_t pf_pop_digit(uint64_t& v) {
+  if ((v >> 32) == 0) {
+    uint32_t x = (uint32_t)v, q = x / 10;
+    v = q;
+    return (uint8_t)('0' + (x - q * 10));
+  }
+  uint64_t q = v / 10;
+  uint8_t ch = (uint8_t)('0' + (uint32_t)(v - q * 10));
+  v = q;
+  return ch;
+}
+
+// store the text so that it ends just before `p`.  Written last byte first:
+// peeling digits off the low end divides by the constant ten, where
+// first-to-last needs a division by a variable power of ten per digit.
+DEV void pf_write(uint8_t* p, const PfText& t) {
+  if (t.form >= PF_NAN) {
+    static const char NF[] = "\"NaN\"\"-Infinity\"";
+    uint32_t from = t.form == PF_NAN ? 0 : 5, n = t.form == PF_NAN ? 5 : 11;
+    // without its sign, "Infinity" keeps the opening quote
+    for (uint32_t i = n; i-- > 0;) {
+      if (t.form == PF_INF && !t.neg && i == 1) continue;
+      *--p = (uint8_t)NF[from + i];
+    }
+    return;
+  }
+  int32_t tz = 0;     // zeros after the digits (ddd000)
+  int32_t frac = -1;  // digits after the point, -1 = no point among them
+  int32_t lz = -1;    // zeros between "0." and the digits, -1 = no "0."
+  if (t.quoted) *--p = '"';
+  if (t.form == PF_FP) {
+    if (t.e10 >= -6 && t.e10 <= 20) {
+      if (t.e10 < 0) lz = -t.e10 - 1;
+      else if (t.ndig > t.e10 + 1) frac = t.ndig - (t.e10 + 1);
+      else tz = t.e10 + 1 - t.ndig;
+    } else {
+      uint32_t e = (uint32_t)(t.e10 < 0 ? -t.e10 : t.e10);
+      uint32_t q = e / 10;
+      *--p = (uint8_t)('0' + (e - q * 10));
+      if (e >= 100) {
+        *--p = (uint8_t)('0' + (q - (q / 10) * 10));
+        *--p = (uint8_t)('0' + q / 10);
+      } else {
+        *--p = (uint8_t)('0' + q);
+      }
+      *--p = t.e10 < 0 ? '-' : '+';
+      *--p = 'e';
+      if (t.ndig > 1) frac = t.ndig - 1;
+    }
+  }
+  for (int32_t i = 0; i < tz; ++i) *--p = '0';
+  uint64_t v = t.digits;
+  for (int32_t i = 0; i < t.ndig; ++i) {
+    if (i == frac) *--p = '.';
+    *--p = pf_pop_digit(v);
+  }
+  if (lz >= 0) {
+    for (int32_t i = 0; i < lz; ++i) *--p = '0';
+    *--p = '.';
+    *--p = '0';
+  }
+  if (t.neg) *--p = '-';
+  if (t.quoted) *--p = '"';
+}
+
+DEVN bool emit_packed_fixed(DCtx& c, uint32_t kind, uint32_t end, bool* first) {
+  const bool wide = kind == K_DOUBLE || kind == K_FIXED64 || kind == K_SFIXED64;
+  const uint32_t shift = wide ? 3 : 2;
+  const uint32_t nbytes = end - c.pos;
+  if (nbytes & ((1u << shift) - 1)) return dfail(c, E_PARSE);
+  const uint32_t n = nbytes >> shift;
+  for (uint32_t base = 0; base < n; base += WAVE) {
+    const uint32_t i = base + (uint32_t)c.lane;
+    const bool act = i < n;
+    PfText t = pf_format(kind, act ? pf_load(c.pb + c.pos + (i << shift), wide) : 0);
+    const uint32_t comma = (i || !*first) ? 1 : 0;
+    const uint32_t len = act ? pf_len(t) + comma : 0;
+    // inclusive wave scan of the lengths
+    uint32_t inc = len;
+    #pragma unroll
+    for (int d = 1; d < WAVE; d <<= 1) {
+      uint32_t up = __shfl_up(inc, d, WAVE);
+      if (c.lane >= d) inc += up;
+    }
+    const uint32_t total = __shfl(inc, WAVE - 1, WAVE);
+    // the wave-uniform total is judged before any lane stores a byte
+    if (c.opos + total > c.ocap) return dfail(c, E_OVERFLOW);
+    if (act) {
+      uint8_t* at = c.out + c.opos + (inc - len);
+      if (comma) *at = ',';
+      pf_write(at + len, t);
+    }
+    c.opos += total;
+  }
+  if (n) *first = false;
+  c.pos = end;
+  return true;
+}
+
 // packed array payload (numeric/enum/bool kinds only per protobuf)
 DEVN bool emit_packed(DCtx& c, const FieldEntry& f, uint32_t end, bool* first) {
+  switch (f.kind) {
+    case K_DOUBLE: case K_FLOAT: case K_FIXED32: case K_SFIXED32:
+    case K_FIXED64: case K_SFIXED64:
+      return emit_packed_fixed(c, f.kind, end, first);
+  }
   while (c.pos < end) {
     if (!*first) {
       if (!putc_(c, ',')) return false;

@@ -44,7 +44,8 @@ def _common_flags():
 def build_jsonproto(verbose: bool = True, force: bool = False) -> Path:
     sources = [CSRC / "engine.cpp", CSRC / "json2pb.hip", CSRC / "pb2json.hip",
                CSRC / "pb2json_wg.h", CSRC / "pb_reorder.h", CSRC / "common.h",
-               CSRC / "fp_shortest.h", CSRC / "pow10_table.h", CSRC / "h2grpc_impl.h", CSRC / "span_api.h",
+               CSRC / "fp_shortest.h", CSRC / "pow10_table.h", CSRC / "fp_parse.h",
+               CSRC / "pow5_table.h", CSRC / "h2grpc_impl.h", CSRC / "span_api.h",
                CSRC / "span_host.h"]
     if not force and not _needs(SO_PATH, sources):
         return SO_PATH
@@ -83,7 +84,8 @@ def build_hostsim(verbose: bool = True, force: bool = False) -> Path:
     """Single-lane CPU build of the kernels (csrc/host_shim.h)."""
     sources = [CSRC / "host_sim.cpp", CSRC / "json2pb.hip", CSRC / "pb2json.hip",
                CSRC / "pb2json_wg.h", CSRC / "pb_reorder.h", CSRC / "common.h", CSRC / "host_shim.h", CSRC / "span_host.h",
-               CSRC / "fp_shortest.h", CSRC / "pow10_table.h"]
+               CSRC / "fp_shortest.h", CSRC / "pow10_table.h", CSRC / "fp_parse.h",
+               CSRC / "pow5_table.h"]
     if not force and not _needs(HOSTSIM_SO_PATH, sources):
         return HOSTSIM_SO_PATH
     cxx = os.environ.get("CXX", "g++")

@@ -36,6 +36,8 @@
 #endif
 #endif
 
+#include "fp_parse.h"  // pk_window: packed numeric arrays, one element per lane
+
 #ifndef WPB
 #define WPB 4
 #endif  // waves (=requests) per 256-thread block
@@ -1617,11 +1619,32 @@ DEVN int encode_body_key(Ctx& c, EFrame& f) {
 
 // whole packed repeated array "[e,e,...]" — '[' already consumed, at first
 // element; emits tag + len slot + packed payload + backfill
+//
+// Numeric kinds go up to WAVE elements per step through pk_window
+// (fp_parse.h).  Whatever a window declines is left where it was for the
+// serial element below, which owns every error; after an empty window the
+// serial loop runs 1, 2, 4, .. 64 elements before the next attempt, so an
+// array the window cannot take costs little more than it did.
 DEVN bool encode_packed_array(Ctx& c, const FieldEntry& f) {
   if (!emit_tag(c, f.number, W_LEN)) return false;
   uint32_t slot;
   if (!reserve_len(c, &slot)) return false;
+  const bool windowed = f.kind != K_BOOL && f.kind != K_ENUM;
+  uint32_t serial_left = 0, backoff = 1;
   while (true) {
+    if (windowed && serial_left == 0) {
+      PkWin w = pk_window(c.s, c.len, c.pos, c.out, c.opos, c.ocap, c.lane, f.kind);
+      c.pos = w.pos;
+      c.opos = w.opos;
+      if (w.state == 2) break;
+      if (w.state == 1) {
+        backoff = 1;
+        continue;
+      }
+      serial_left = backoff;
+      if (backoff < 64) backoff <<= 1;
+    }
+    if (serial_left) --serial_left;
     skip_ws(c);
     if (!encode_packed_element(c, f)) return false;
     skip_ws(c);

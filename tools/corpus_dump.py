@@ -19,6 +19,7 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path[:0] = [str(ROOT), str(ROOT / "tests")]
 
 import any_corpus as ac  # noqa: E402
+import packed_encode_corpus as pe  # noqa: E402
 import protojson_corpus as pc  # noqa: E402
 import wide_schema_corpus as wc  # noqa: E402
 from ggrmcp_amd.engine.tables import compile_tables  # noqa: E402
@@ -61,6 +62,22 @@ def _wide_cases(env):
     return cases
 
 
+def _packed_encode_docs():
+    """tests/packed_encode_corpus.py: every list the packed-array encode tests
+    run, and every prefix of one two-window array."""
+    docs = [pe.doc("double", pe.EXTREMES_65), pe.doc("double", pe.quoted(pe.EXTREMES_65)),
+            pe.TIE_DOC, pe.OVERFLOW_DOC, pe.WG_DOC]
+    for kind, texts in (("double", pe.DOUBLE_TEXTS), ("float", pe.FLOAT_TEXTS)):
+        docs += [pe.doc(kind, texts[i:i + 64]) for i in range(0, len(texts), 64)]
+    for kind in pe.KINDS:
+        docs += pe.geometry_docs(kind)
+    for at in pe.ODD_AT:
+        docs += [pe.odd_doc(o, at) for o in pe.ODD_OK + [o for o, _ in pe.ODD_BAD]]
+        docs.append(pe.odd_doc(str(at), at, ""))
+    text = pe.geometry_docs("double")[3]
+    return docs + [text[:k] for k in range(len(text))]
+
+
 def main(out_path: str) -> None:
     env = pc.make_env(_Tables)
     t = env.engine.tables
@@ -74,6 +91,7 @@ def main(out_path: str) -> None:
         cases.append((1, env.inner_idx, pc.ld(1, b)))
     for b in pc.whitespace_cases():
         cases.append((0, env.inner_idx, b))
+    cases += [(0, env.sink_idx, d.encode()) for d in _packed_encode_docs()]
     any_env = ac.make_env(_Tables)
     any_cases = _any_cases(any_env)
     wide_env = wc.make_env(_Tables)

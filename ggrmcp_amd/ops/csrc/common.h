@@ -352,6 +352,23 @@ DEV bool get_varint(const uint8_t* p, uint32_t len, uint32_t* pos, uint64_t* out
   return false;
 }
 
+// position of the r-th (0-based) set bit of m; r < popcount(m).  Rank-select
+// for the one-element-per-lane windows (fp_parse.h pk_window, pb2json.hip
+// pv_window): lane r finds the r-th boundary of a ballot mask.
+DEV uint32_t pk_select64(uint64_t m, uint32_t r) {
+  uint32_t p = 0;
+  #pragma unroll
+  for (uint32_t w = 32; w; w >>= 1) {
+    const uint32_t cnt =
+        (uint32_t)__builtin_popcountll((m >> p) & ((1ull << w) - 1));
+    if (r >= cnt) {
+      r -= cnt;
+      p += w;
+    }
+  }
+  return p;
+}
+
 __constant__ double DD_POW10[23] = {
     1e0,  1e1,  1e2,  1e3,  1e4,  1e5,  1e6,  1e7,  1e8,  1e9,  1e10, 1e11,
     1e12, 1e13, 1e14, 1e15, 1e16, 1e17, 1e18, 1e19, 1e20, 1e21, 1e22};

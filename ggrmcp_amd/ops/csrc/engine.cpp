@@ -1480,6 +1480,45 @@ __global__ void k_dd_probe(double d, int prec, uint64_t* out) {
   out[7] = __builtin_bit_cast(uint64_t, e1);
 }
 
+// packed_varint_probe: emit_packed_varint alone, one block of one wave, with
+// the element count of every window traced (pb2json.hip pv_probe)
+__global__ void __launch_bounds__(WAVE)
+k_pv_probe(const uint8_t* body, uint32_t n, uint32_t kind, uint8_t* text,
+           uint32_t cap, uint32_t* trace, uint32_t* res) {
+  pv_probe(body, n, kind, text, cap, trace, res, (int)threadIdx.x);
+}
+
+static py::tuple packed_varint_probe(const std::string& kind,
+                                     const std::string& body, uint32_t cap) {
+  const uint32_t k = pv_probe_kind(kind.c_str());
+  if (!k) throw std::invalid_argument("packed_varint_probe: kind " + kind);
+  // one allocation: body | text | trace | res, each part 16-byte aligned
+  const size_t n = body.size();
+  const size_t text_at = (n + 15) & ~(size_t)15;
+  const size_t trace_at = text_at + (((size_t)cap + 15) & ~(size_t)15);
+  const size_t res_at = trace_at + PV_TRACE_CAP * sizeof(uint32_t);
+  uint8_t* d;
+  HIP_CHECK(hipMalloc(&d, res_at + 16));
+  std::vector<uint8_t> h(res_at + 16 - text_at);
+  hipError_t e = n ? hipMemcpy(d, body.data(), n, hipMemcpyHostToDevice) : hipSuccess;
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_pv_probe, dim3(1), dim3(WAVE), 0, nullptr, d,
+                       (uint32_t)n, k, d + text_at, cap,
+                       (uint32_t*)(d + trace_at), (uint32_t*)(d + res_at));
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess)
+    e = hipMemcpy(h.data(), d + text_at, h.size(), hipMemcpyDeviceToHost);
+  (void)hipFree(d);
+  HIP_CHECK(e);
+  const uint32_t* res = (const uint32_t*)(h.data() + (res_at - text_at));
+  const uint32_t* trace = (const uint32_t*)(h.data() + (trace_at - text_at));
+  py::list windows;
+  for (uint32_t i = 0; i < res[2]; ++i) windows.append(trace[i]);
+  return py::make_tuple((int)res[0], py::bytes((const char*)h.data(), res[1]),
+                        windows);
+}
+
 static int device_count() {
   int n = 0;
   hipError_t e = hipGetDeviceCount(&n);
@@ -1509,6 +1548,9 @@ PYBIND11_MODULE(_jsonproto, m) {
     r["e1"] = py::cast(*(double*)&h[7]);
     return r;
   });
+  m.def("packed_varint_probe", &packed_varint_probe, py::arg("kind"),
+        py::arg("body"), py::arg("cap"));
+  m.attr("PV_STRETCH") = (int)PV_STRETCH;
   // diagnostic: verify the cross-module cast of an _h2grpc Client works in
   // this process (pybind shares its type registry across extensions when
   // the class typeinfo is default-visibility)

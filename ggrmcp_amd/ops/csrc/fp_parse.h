@@ -275,21 +275,6 @@ DEV void pk_scan64(const uint8_t* s, uint32_t n, uint32_t base, int lane,
   cls = mc;
 }
 
-// position of the r-th (0-based) set bit of m; r < popcount(m)
-DEV uint32_t pk_select64(uint64_t m, uint32_t r) {
-  uint32_t p = 0;
-  #pragma unroll
-  for (uint32_t w = 32; w; w >>= 1) {
-    const uint32_t cnt =
-        (uint32_t)__builtin_popcountll((m >> p) & ((1ull << w) - 1));
-    if (r >= cnt) {
-      r -= cnt;
-      p += w;
-    }
-  }
-  return p;
-}
-
 constexpr uint32_t PK_STRETCH = 256;
 
 struct PkWin {

@@ -228,6 +228,23 @@ PYBIND11_MODULE(_hostsim, m) {
     return py::make_tuple(offs, writes, pack_total(packed.data(), n));
   }, py::arg("lens"), py::arg("dst_cap"));
 
+  // emit_packed_varint alone (pb2json.hip pv_probe), as the device
+  // extension's probe: (status, text, element count of every window)
+  m.def("packed_varint_probe", [](const std::string& kind,
+                                  const std::string& body, uint32_t cap) {
+    const uint32_t k = pv_probe_kind(kind.c_str());
+    if (!k) throw std::invalid_argument("packed_varint_probe: kind " + kind);
+    std::vector<uint8_t> in(body.begin(), body.end()), text(cap);
+    std::vector<uint32_t> trace(PV_TRACE_CAP);
+    uint32_t res[3] = {0, 0, 0};
+    pv_probe(in.data(), (uint32_t)in.size(), k, text.data(), cap, trace.data(),
+             res, 0);
+    trace.resize(res[2]);
+    return py::make_tuple((int)res[0],
+                          py::bytes((const char*)text.data(), res[1]), trace);
+  }, py::arg("kind"), py::arg("body"), py::arg("cap"));
+  m.attr("PV_STRETCH") = (int)PV_STRETCH;
+
   // the native spans' pure host pieces (span_host.h), for the CPU tier
   m.def("grpc_reply", [](int status, const std::string& data,
                          const std::string& msg) {

@@ -1052,12 +1052,248 @@ DEVN bool emit_packed_fixed(DCtx& c, uint32_t kind, uint32_t end, bool* first) {
   return true;
 }
 
+// ---------------------------------------------------------------------------
+// Packed varint runs (int32/64, uint32/64, sint32/64, bool, enum): one
+// element per lane.  Element i is not at pos + width * i, but a varint ends at
+// the first byte with its top bit clear, so a ballot of that predicate over a
+// stretch of the run is the list of element ends (docs/KERNELS.md, "Packed
+// varint runs"):
+//
+//   scan     PV_STRETCH bytes from `pos`, one byte per lane per load, become
+//            PV_STRETCH/64 position-ordered 64-bit masks of "terminator below
+//            the run's end".  Bytes at or past `end` are not loaded
+//   own      lane k owns the element that ends at terminator k: the word
+//            comes from the masks' prefix popcounts, the bit from pk_select64,
+//            the start from lane k-1.  An element cut by the stretch edge has
+//            no terminator here and opens the next stretch
+//   parse    the lane folds its own 1..10 bytes as get_varint does; a longer
+//            piece makes it decline.  Byte loads, not two wide ones: they need
+//            no guard at the slot's edges or for alignment, they touch no
+//            byte outside the lane's own piece, the ten are independent (so
+//            they issue back to back into lines the scan just fetched), and
+//            the common one-byte element costs a single load
+//   format   emit_scalar_value's value rules into a PfText; true/false from
+//            a register; an enum name from the lane's own search of the table
+//   commit   a ballot of "valid" gives the longest all-valid prefix, an
+//            inclusive __shfl_up scan of the lengths places the texts, the
+//            wave-uniform total is held against `ocap` before any lane
+//            stores, and every lane stores its own bytes
+//
+// The window never writes E_PARSE.  What it cannot take (an over-long varint,
+// a tail without a terminator, continuation bytes that run past `end`) stays
+// at `pos`, and a window that commits nothing hands the run to emit_packed's
+// serial loop, which reports it as it always did.  No LDS; masks and counts
+// are wave-uniform scalars.  At WAVE=1 a window is one element.
+// ---------------------------------------------------------------------------
+
+#ifndef PV_STRETCH
+#define PV_STRETCH 256
+#endif
+constexpr uint32_t PV_WORDS = PV_STRETCH / 64;
+static_assert(PV_STRETCH % 64 == 0 && PV_WORDS >= 1 && PV_WORDS <= 16, "PV_STRETCH");
+
+struct PvWin {
+  uint32_t pos, opos;  // wave-uniform, advanced past what was committed
+  int32_t state;       // elements committed; -1 = their text does not fit
+};
+
+// `pos` is an element start below `end`; `ev`/`n_ev` are the enum's values
+// (K_ENUM only).  `lead_comma`: the window's first text follows another.
+DEVN PvWin pv_window(const uint8_t* pb, uint32_t pos, uint32_t end, uint8_t* out,
+                     uint32_t opos, uint32_t ocap, int lane, uint32_t kind,
+                     bool lead_comma, const EnumValueEntry* ev, int32_t n_ev,
+                     const uint8_t* names) {
+  PvWin res;
+  res.pos = pos;
+  res.opos = opos;
+  res.state = 0;
+  const uint32_t room = end > pos ? end - pos : 0;  // bytes that may be read
+
+  // scan: term[j] bit i = byte pos + 64 j + i ends an element; upto[j] = the
+  // terminators in words 0..j
+  uint64_t term[PV_WORDS];
+  uint32_t upto[PV_WORDS];
+  uint32_t found = 0;
+  #pragma unroll
+  for (uint32_t j = 0; j < PV_WORDS; ++j) {
+    uint64_t m = 0;
+    for (uint32_t i = (uint32_t)lane; i < 64; i += WAVE) {
+      const uint32_t o = 64 * j + i;
+      if (o < room && !(pb[pos + o] & 0x80)) m |= 1ull << i;
+    }
+#if WAVE > 1
+    m = __ballot(m != 0);
+#endif
+    term[j] = m;
+    found += (uint32_t)__builtin_popcountll(m);
+    upto[j] = found;
+  }
+  const uint32_t cnt = found < WAVE ? found : WAVE;
+  if (cnt == 0) return res;
+
+  // own: offsets from `pos` of the lane's terminator and first byte
+  const uint32_t k = (uint32_t)lane;
+  const bool act = k < cnt;
+  uint32_t last = 0;
+  if (act) {
+    uint64_t m = term[0];
+    uint32_t below = 0, base = 0;
+    #pragma unroll
+    for (uint32_t j = 1; j < PV_WORDS; ++j) {
+      if (k >= upto[j - 1]) {
+        m = term[j];
+        below = upto[j - 1];
+        base = 64 * j;
+      }
+    }
+    last = base + pk_select64(m, k - below);
+  }
+  const uint32_t prev = __shfl_up(last, 1, WAVE);
+  const uint32_t from = lane ? prev + 1 : 0;
+  const uint32_t nb = last - from + 1;
+
+  // parse: bits the tenth byte shifts past bit 63 are dropped
+  const bool ok = act && nb <= 10;
+  uint64_t v = 0;
+  if (ok) {
+    const uint8_t* p = pb + pos + from;
+    #pragma unroll
+    for (uint32_t i = 0; i < 10; ++i) {
+      if (i < nb) v |= (uint64_t)(p[i] & 0x7F) << (7 * i);
+    }
+  }
+
+  // format
+  PfText t;
+  t.digits = 0;
+  t.ndig = 1;
+  t.e10 = 0;
+  t.form = PF_INT;
+  t.neg = false;
+  t.quoted = kind == K_INT64 || kind == K_UINT64 || kind == K_SINT64;
+  uint64_t word = 0;            // K_BOOL: the literal, first byte lowest
+  const uint8_t* name = nullptr;  // K_ENUM: the value's name
+  uint32_t tlen = 0;
+  if (ok) {
+    int64_t sv = 0;
+    bool has_sign = true;
+    switch (kind) {
+      case K_INT64: sv = (int64_t)v; break;
+      case K_SINT64: sv = unzigzag64(v); break;
+      case K_INT32: sv = (int64_t)(int32_t)(uint32_t)v; break;
+      case K_SINT32:
+        sv = (int64_t)(int32_t)((uint32_t)(v >> 1) ^ (uint32_t)(0 - (v & 1)));
+        break;
+      case K_ENUM: {
+        const int32_t num = (int32_t)(int64_t)v;
+        sv = num;  // unknown enum value -> number (protojson)
+        for (int32_t i = 0; i < n_ev; ++i) {
+          if (ev[i].number == num) {
+            name = names + ev[i].name_off;
+            tlen = (uint32_t)ev[i].name_len + 2;
+            break;
+          }
+        }
+        break;
+      }
+      case K_UINT32: v = (uint32_t)v; has_sign = false; break;
+      default: has_sign = false; break;  // K_UINT64, K_BOOL
+    }
+    if (has_sign) {
+      t.neg = sv < 0;
+      v = t.neg ? (uint64_t)(~sv) + 1ull : (uint64_t)sv;
+    }
+    if (kind == K_BOOL) {
+      word = v ? 0x65757274ull : 0x65736c6166ull;  // "true" : "false"
+      tlen = v ? 4 : 5;
+    } else if (!name) {
+      t.digits = v;
+      t.ndig = (int32_t)pf_count_digits(v);
+      tlen = pf_len(t);
+    }
+  }
+
+  // commit: the longest all-valid prefix
+  const uint64_t bad = ~__ballot(ok);
+  uint32_t take = bad ? (uint32_t)__ffsll((long long)bad) - 1 : 64;
+  if (take > cnt) take = cnt;
+  if (take == 0) return res;
+  const bool mine = k < take;
+  const uint32_t comma = (k || lead_comma) ? 1 : 0;
+  const uint32_t len = mine ? tlen + comma : 0;
+  uint32_t inc = len;
+  #pragma unroll
+  for (int d = 1; d < WAVE; d <<= 1) {
+    const uint32_t up = __shfl_up(inc, d, WAVE);
+    if (lane >= d) inc += up;
+  }
+  const uint32_t total = __shfl(inc, WAVE - 1, WAVE);
+  // the wave-uniform total is judged before any lane stores a byte
+  if (opos + total > ocap) {
+    res.state = -1;
+    return res;
+  }
+  if (mine) {
+    uint8_t* at = out + opos + (inc - len);
+    uint8_t* p = at + len;  // last byte first, as pf_write
+    if (name) {
+      *--p = '"';
+      for (uint32_t i = tlen - 2; i-- > 0;) *--p = name[i];
+      *--p = '"';
+    } else if (kind == K_BOOL) {
+      for (uint32_t i = tlen; i-- > 0;) *--p = (uint8_t)(word >> (8 * i));
+    } else {
+      pf_write(p, t);
+    }
+    if (comma) *at = ',';
+  }
+  res.opos = opos + total;
+  res.pos = pos + (uint32_t)__shfl(last, (int)take - 1, WAVE) + 1;
+  res.state = (int32_t)take;
+  return res;
+}
+
+// windows from c.pos until one commits nothing; `trace` (the probe's, else
+// null) gets each window's element count, *n_trace counts them
+DEV bool pv_windows(DCtx& c, const FieldEntry& f, uint32_t end, bool* first,
+                    uint32_t* trace, uint32_t trace_cap, uint32_t* n_trace) {
+  const EnumValueEntry* ev = nullptr;
+  int32_t n_ev = 0;
+  if (f.kind == K_ENUM) {
+    const EnumEntry& ee = c.t.enums[f.sub_index];
+    ev = c.t.enum_vals + ee.val_start;
+    n_ev = ee.val_count;
+  }
+  while (c.pos < end) {
+    const PvWin w = pv_window(c.pb, c.pos, end, c.out, c.opos, c.ocap, c.lane,
+                              f.kind, !*first, ev, n_ev, c.t.names);
+    if (w.state < 0) return dfail(c, E_OVERFLOW);
+    if (w.state == 0) break;
+    c.pos = w.pos;
+    c.opos = w.opos;
+    *first = false;
+    if (trace) {
+      if (!c.lane && *n_trace < trace_cap) trace[*n_trace] = (uint32_t)w.state;
+      ++*n_trace;
+    }
+  }
+  return true;
+}
+
+DEVN bool emit_packed_varint(DCtx& c, const FieldEntry& f, uint32_t end,
+                             bool* first) {
+  return pv_windows(c, f, end, first, nullptr, 0, nullptr);
+}
+
 // packed array payload (numeric/enum/bool kinds only per protobuf)
 DEVN bool emit_packed(DCtx& c, const FieldEntry& f, uint32_t end, bool* first) {
   switch (f.kind) {
     case K_DOUBLE: case K_FLOAT: case K_FIXED32: case K_SFIXED32:
     case K_FIXED64: case K_SFIXED64:
       return emit_packed_fixed(c, f.kind, end, first);
+    case K_INT32: case K_INT64: case K_UINT32: case K_UINT64: case K_SINT32:
+    case K_SINT64: case K_BOOL: case K_ENUM:
+      if (!emit_packed_varint(c, f, end, first)) return false;
   }
   while (c.pos < end) {
     if (!*first) {
@@ -1067,6 +1303,55 @@ DEVN bool emit_packed(DCtx& c, const FieldEntry& f, uint32_t end, bool* first) {
     if (!emit_scalar_value(c, f)) return false;
   }
   return c.pos == end || dfail(c, E_PARSE);
+}
+
+// packed_varint_probe's body on both tiers (engine.cpp k_pv_probe, one wave;
+// host_sim.cpp): the windows of emit_packed_varint over body[0, n) into `cap`
+// bytes with first = true, each window's element count traced.  What the
+// windows leave goes to emit_packed as in the walker, traced as one 0: the
+// serial loop ends a run the windows stopped at.  res = {status, text bytes,
+// trace entries}.
+constexpr uint32_t PV_TRACE_CAP = 1024;
+DEV void pv_probe(const uint8_t* body, uint32_t n, uint32_t kind, uint8_t* text,
+                  uint32_t cap, uint32_t* trace, uint32_t* res, int lane) {
+  DCtx c;
+  c.pb = body;
+  c.len = n;
+  c.pos = 0;
+  c.out = text;
+  c.opos = 0;
+  c.ocap = cap;
+  c.t = Tables{};
+  c.status = E_OK;
+  c.lane = lane;
+  FieldEntry f{};
+  f.kind = (uint8_t)kind;
+  f.sub_index = -1;
+  bool first = true;
+  uint32_t n_trace = 0;
+  if (pv_windows(c, f, n, &first, trace, PV_TRACE_CAP, &n_trace) && c.pos < n) {
+    if (!lane && n_trace < PV_TRACE_CAP) trace[n_trace] = 0;
+    ++n_trace;
+    emit_packed(c, f, n, &first);
+  }
+  if (!lane) {
+    res[0] = (uint32_t)c.status;
+    res[1] = c.opos;
+    res[2] = n_trace < PV_TRACE_CAP ? n_trace : PV_TRACE_CAP;
+  }
+}
+
+// host side of the probe: the kinds it takes, by proto type name (enum needs
+// the tables and is covered through the engine); 0 = not one of them
+static inline uint32_t pv_probe_kind(const char* name) {
+  static const struct { const char* name; uint32_t kind; } KINDS[] = {
+      {"int32", K_INT32}, {"int64", K_INT64}, {"uint32", K_UINT32},
+      {"uint64", K_UINT64}, {"sint32", K_SINT32}, {"sint64", K_SINT64},
+      {"bool", K_BOOL}};
+  for (const auto& k : KINDS) {
+    if (!__builtin_strcmp(name, k.name)) return k.kind;
+  }
+  return 0;
 }
 
 // map key bytes -> JSON object key (always quoted)

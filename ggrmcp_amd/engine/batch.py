@@ -223,6 +223,15 @@ class GpuEngine:
         item walk, 2 = the in-block classic pass (0 = ``k_pb2json``)."""
         return int(self._eng.wg_decode_slots)
 
+    def wg_scan_probe(self, wire: bytes, msg_idx: int,
+                      mode: int = 0) -> List[Tuple[int, int, int]]:
+        """The items the workgroup decode kernel's scanner makes of one
+        response: ``[(start, end, kind)]`` in wire offsets, kind 0 = a field
+        run (or an entry chunk of one), 1 = a fill item, 2 = a chunk of a
+        packed run.  Empty: the request takes the in-block classic pass."""
+        return [tuple(int(x) for x in it)
+                for it in self._eng.wg_scan_probe(bytes(wire), int(msg_idx), mode)]
+
     # -- low-level batch ops -------------------------------------------------
 
     def encode_batch(

@@ -58,6 +58,12 @@ class HostSimEngine:
             type_table=t.type_table,
         )
 
+    def wg_scan_probe(self, wire: bytes, msg_idx: int,
+                      mode: int = 0) -> List[Tuple[int, int, int]]:
+        """``GpuEngine.wg_scan_probe`` on the CPU build: ``wgd_scan`` alone."""
+        return [tuple(int(x) for x in it)
+                for it in self._eng.wg_scan_probe(bytes(wire), int(msg_idx), mode)]
+
     def encode_batch(
         self,
         payloads: Sequence[bytes],

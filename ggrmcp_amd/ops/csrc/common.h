@@ -475,6 +475,13 @@ constexpr int WG_DEC_WAVES = 16;  // waves per request workgroup
 // All 64 defaults of bench.Wide64 print in ~1.3 KB; a top message whose
 // defaults outgrow the area leaves with E_OVERFLOW like any other slot.
 constexpr uint32_t WG_DEC_FILL = 8192;
+// A top-level packed run (one length-delimited record of a repeated scalar) of
+// two chunks or more is cut into items of about this many body bytes at
+// element boundaries, so the block's waves share it (pb2json_wg.h wgd_scan;
+// profiles/wg_packed_chunks.md for the value).
+constexpr uint32_t WG_DEC_PACK_CHUNK = 4096;
+static_assert(WG_DEC_PACK_CHUNK >= 64 && WG_DEC_PACK_CHUNK % 8 == 0,
+              "WG_DEC_PACK_CHUNK");
 
 // Workgroup-cooperative ENCODE (k_json2pb_wg): JSON-RPC requests at least
 // WG_ENC_MIN_BYTES long split their arguments object into top-level-member

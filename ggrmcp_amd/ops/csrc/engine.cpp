@@ -24,6 +24,7 @@
 
 #include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
+#include <pybind11/stl.h>
 
 #include <chrono>
 #include <cstring>
@@ -932,6 +933,11 @@ class Engine : public spanapi::ISpanExecutor {
     return py::make_tuple(last_enc_gpu_ms_, last_dec_gpu_ms_);
   }
 
+  // the items k_pb2json_wg's scanner makes of one response of message
+  // msg_idx: [(start, end, kind)], empty for the classic pass
+  std::vector<std::array<uint32_t, 3>> wg_scan_probe(const std::string& wire,
+                                                     int msg_idx, int mode);
+
   int device() const { return device_; }
   int max_batch() const { return max_batch_; }
   // cumulative count of slots routed to k_pb2json_wg (+= n_wg per batch)
@@ -1519,6 +1525,49 @@ static py::tuple packed_varint_probe(const std::string& kind,
                         windows);
 }
 
+// wg_scan_probe: k_pb2json_wg's scanner alone over one wire, one block of one
+// wave, and the item table it leaves (pb2json_wg.h wgd_scan_dump)
+__global__ void __launch_bounds__(WAVE)
+k_wg_scan_probe(const uint8_t* pb, uint32_t wire_len, int msg_idx, int flags,
+                Tables t, uint32_t* out) {
+  __shared__ WgDecState S;
+  WgDecReq q{};
+  q.pb = pb;
+  q.wire_len = wire_len;
+  q.msg_idx = msg_idx;
+  q.flags = flags;
+  wgd_scan(S, q, t);
+  __syncthreads();
+  wgd_scan_dump(S, out);
+}
+
+std::vector<std::array<uint32_t, 3>> Engine::wg_scan_probe(
+    const std::string& wire, int msg_idx, int mode) {
+  if (msg_idx < 0 || msg_idx >= tables_.n_msgs)
+    throw std::invalid_argument("wg_scan_probe: msg_idx");
+  HIP_CHECK(hipSetDevice(device_));
+  // one allocation: wire | item table, the table 16-byte aligned
+  const size_t n = wire.size();
+  const size_t out_at = (n + 15) & ~(size_t)15;
+  std::vector<uint32_t> h(WG_SCAN_PROBE_WORDS);
+  uint8_t* d;
+  HIP_CHECK(hipMalloc(&d, out_at + h.size() * sizeof(uint32_t)));
+  hipError_t e = n ? hipMemcpy(d, wire.data(), n, hipMemcpyHostToDevice) : hipSuccess;
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_wg_scan_probe, dim3(1), dim3(WAVE), 0, nullptr, d,
+                       (uint32_t)n, msg_idx,
+                       mode & (DM_UNPOPULATED | DM_STRUCTURED), tables_,
+                       (uint32_t*)(d + out_at));
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess)
+    e = hipMemcpy(h.data(), d + out_at, h.size() * sizeof(uint32_t),
+                  hipMemcpyDeviceToHost);
+  (void)hipFree(d);
+  HIP_CHECK(e);
+  return wgd_scan_items(h.data());
+}
+
 static int device_count() {
   int n = 0;
   hipError_t e = hipGetDeviceCount(&n);
@@ -1551,6 +1600,8 @@ PYBIND11_MODULE(_jsonproto, m) {
   m.def("packed_varint_probe", &packed_varint_probe, py::arg("kind"),
         py::arg("body"), py::arg("cap"));
   m.attr("PV_STRETCH") = (int)PV_STRETCH;
+  m.attr("WG_DEC_PACK_CHUNK") = (int)WG_DEC_PACK_CHUNK;
+  m.attr("WG_DEC_MAX_ITEMS") = (int)WG_DEC_MAX_ITEMS;
   // diagnostic: verify the cross-module cast of an _h2grpc Client works in
   // this process (pybind shares its type registry across extensions when
   // the class typeinfo is default-visibility)
@@ -1597,6 +1648,8 @@ PYBIND11_MODULE(_jsonproto, m) {
       .def("set_structured_content", &Engine::set_structured_content,
            py::arg("on"))
       .def("set_reorder_wire", &Engine::set_reorder_wire, py::arg("on"))
+      .def("wg_scan_probe", &Engine::wg_scan_probe, py::arg("wire"),
+           py::arg("msg_idx"), py::arg("mode") = 0)
       .def("last_stage_ms", &Engine::last_stage_ms)
       .def("last_gpu_ms", &Engine::last_gpu_ms)
       .def("span_handle",

@@ -10,6 +10,7 @@
 #include <pybind11/stl.h>
 
 #include <cstring>
+#include <memory>
 #include <optional>
 #include <string>
 #include <vector>
@@ -101,6 +102,27 @@ class HostEngine {
       throw std::runtime_error("decode_wg: envelope mode with a skip array");
     return decode_impl(data, resp_off, scratch_off, final_off, msg_idx, skip,
                        mode, true);
+  }
+
+  // k_pb2json_wg's scanner alone (pb2json_wg.h wgd_scan), as the device
+  // extension's probe: [(start, end, kind)], empty for the classic pass
+  std::vector<std::array<uint32_t, 3>> wg_scan_probe(const std::string& wire,
+                                                     int msg_idx, int mode) {
+    if (msg_idx < 0 || msg_idx >= t_.n_msgs)
+      throw std::invalid_argument("wg_scan_probe: msg_idx");
+    // exact-size copy of the wire: the scanner reads no byte past it
+    std::vector<uint8_t> in(wire.begin(), wire.end());
+    std::vector<uint32_t> out(WG_SCAN_PROBE_WORDS);
+    auto S = std::make_unique<WgDecState>();
+    WgDecReq q{};
+    q.pb = in.data();
+    q.wire_len = (uint32_t)in.size();
+    q.msg_idx = msg_idx;
+    q.flags = mode & (DM_UNPOPULATED | DM_STRUCTURED);
+    threadIdx.x = 0;
+    wgd_scan(*S, q, t_);
+    wgd_scan_dump(*S, out.data());
+    return wgd_scan_items(out.data());
   }
 
  private:
@@ -206,7 +228,9 @@ PYBIND11_MODULE(_hostsim, m) {
            py::arg("skip") = py::none(), py::arg("mode") = 0)
       .def("decode_wg", &HostEngine::decode_wg, py::arg("data"),
            py::arg("resp_off"), py::arg("scratch_off"), py::arg("final_off"),
-           py::arg("msg_idx"), py::arg("skip"), py::arg("mode") = 0);
+           py::arg("msg_idx"), py::arg("skip"), py::arg("mode") = 0)
+      .def("wg_scan_probe", &HostEngine::wg_scan_probe, py::arg("wire"),
+           py::arg("msg_idx"), py::arg("mode") = 0);
 
   // k_pack_out's offset arithmetic (pb2json.hip pack_partial / pack_place,
   // summed over the kernel's 256 thread indices) for a batch of out_len
@@ -244,6 +268,8 @@ PYBIND11_MODULE(_hostsim, m) {
                           py::bytes((const char*)text.data(), res[1]), trace);
   }, py::arg("kind"), py::arg("body"), py::arg("cap"));
   m.attr("PV_STRETCH") = (int)PV_STRETCH;
+  m.attr("WG_DEC_PACK_CHUNK") = (int)WG_DEC_PACK_CHUNK;
+  m.attr("WG_DEC_MAX_ITEMS") = (int)WG_DEC_MAX_ITEMS;
 
   // the native spans' pure host pieces (span_host.h), for the CPU tier
   m.def("grpc_reply", [](int status, const std::string& data,

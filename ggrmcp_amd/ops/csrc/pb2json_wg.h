@@ -16,6 +16,10 @@
 //      offsets (comma-joined, skipping default-omitted empty items);
 //   D. wave 0 writes the JSON-RPC envelope framing while every wave
 //      escape-copies its slices into place.
+// A top-level packed run of two chunks or more (one record of a repeated
+// scalar) is cut into PACKED CHUNK items at element boundaries, found without
+// parsing (wgd_pack_split); a chunk is printed by emit_packed directly
+// (wgd_pack_walk) and the joiner's item comma joins the chunks.
 // Requests the scanner cannot split safely (WKT-typed top message,
 // out-of-order top fields, > WG_DEC_MAX_ITEMS runs) take the classic
 // single-wave pass inside the same block, preserving exact semantics.
@@ -42,6 +46,9 @@
 // ---------------------------------------------------------------------------
 #pragma once
 
+#include <array>
+#include <vector>
+
 static __device__ const char WG_P1[] = "{\"jsonrpc\":\"2.0\",\"id\":";
 static __device__ const char WG_P2[] =
     ",\"result\":{\"content\":[{\"type\":\"text\",\"text\":\"";
@@ -53,6 +60,10 @@ static __device__ const char WG_S2[] = ",\"isError\":false}}";
 // produced text, so the escape passes load-balance across waves even
 // when one map/array run carries most of the payload
 constexpr int WG_DEC_MAX_SLICES = 1024;
+
+// WgDecState::pchunk: not a packed chunk, or the run's first / a middle / its
+// last chunk
+enum : uint8_t { WGD_PK_NONE = 0, WGD_PK_FIRST = 1, WGD_PK_MID = 2, WGD_PK_LAST = 3 };
 
 struct WgDecState {
   uint32_t start[WG_DEC_MAX_ITEMS + 1];  // item wire ranges
@@ -67,6 +78,11 @@ struct WgDecState {
   // head bytes of leading name syntax and tail closing brackets
   uint16_t head[WG_DEC_MAX_ITEMS];
   uint8_t tail[WG_DEC_MAX_ITEMS];
+  // a PACKED CHUNK is an element-aligned piece of one top-level packed run:
+  // pchunk says which (WGD_PK_*), pfield is the run's field, counted from the
+  // top message's first.  Its walk prints elements only, so head/tail are 0
+  uint8_t pchunk[WG_DEC_MAX_ITEMS];
+  uint16_t pfield[WG_DEC_MAX_ITEMS];
   uint16_t sl_item[WG_DEC_MAX_SLICES];
   uint32_t sl_off[WG_DEC_MAX_SLICES];   // offset within the item text
   uint32_t sl_esc[WG_DEC_MAX_SLICES];   // escaped length of the slice
@@ -125,6 +141,50 @@ DEV void wgd_ctx(DCtx& c, const Tables& t, uint8_t* out, uint32_t cap) {
   c.lane = lane_id();
 }
 
+// ---- phase A, packed runs: cut one record's body into chunk items ----------
+// Item n - 1 is the run's only record so far (start = its tag); the body is
+// pb[body, body + blen) and belongs to field `fi` of the top message.  Nothing
+// is parsed: a fixed-width element boundary is a multiple of the width (the
+// chunk size is a multiple of 8), a varint one is any byte after one whose
+// top bit is clear.  From a candidate the varint search steps at most ten
+// bytes and stays below the body's end; where it finds none the rest of the
+// run is the last chunk, and that chunk's walk reports the over-long varint or
+// the missing terminator as the unsplit run's did.
+//
+// floor(blen / WG_DEC_PACK_CHUNK) chunks of equal size, or as many as the
+// item table still has room for (then the chunks are proportionally larger),
+// `keep` items held back for the fields after the run.  Returns the new n.
+DEV int wgd_pack_split(WgDecState& S, int n, const uint8_t* pb, uint32_t body,
+                       uint32_t blen, bool varint, int fi, int keep) {
+  int room = WG_DEC_MAX_ITEMS - n;  // items past the first chunk
+  room -= keep < room / 2 ? keep : room / 2;
+  uint32_t nch = blen / WG_DEC_PACK_CHUNK;
+  if (nch > (uint32_t)room + 1) nch = (uint32_t)room + 1;
+  if (nch < 2) return n;
+  // at most nch - 1 multiples of cs lie in [cs, blen)
+  const uint32_t cs = ((blen + nch - 1) / nch + 7u) & ~7u;
+  const int first = n - 1;
+  for (uint32_t b = cs; b < blen; b += cs) {
+    uint32_t p = b;
+    if (varint) {
+      const uint32_t lim = b + 10 < blen - 1 ? b + 10 : blen - 1;
+      while (p <= lim && (pb[body + p - 1] & 0x80)) ++p;
+      if (p > lim) break;
+    }
+    S.head[n] = 0;
+    S.tail[n] = 0;
+    S.pchunk[n] = WGD_PK_MID;
+    S.pfield[n] = (uint16_t)fi;
+    S.start[n++] = body + p;
+  }
+  if (n - 1 > first) {
+    S.pchunk[first] = WGD_PK_FIRST;
+    S.pfield[first] = (uint16_t)fi;
+    S.pchunk[n - 1] = WGD_PK_LAST;
+  }
+  return n;
+}
+
 // ---- phase A: top-level field-run scan (one thread) -----------------------
 // Runs group contiguous same-number tags; MAP / REPEATED runs split into
 // ~4 KB chunks at entry boundaries (chunk walks re-emit the name syntax;
@@ -144,6 +204,7 @@ DEV void wgd_scan(WgDecState& S, const WgDecReq& q, const Tables& t) {
   bool cur_split = false;    // cur run may chunk at entry boundaries
   uint32_t chunk_wire = 0;   // wire bytes accumulated in the open chunk
   const FieldEntry* cur_fe = nullptr;
+  int cur_fi = 0;            // cur_fe's index in the top message
   const MsgEntry& tm = t.msgs[q.msg_idx];
   bool ok = tm.wkt_kind == WKT_NONE;
   while (ok && pos < wire_len) {
@@ -152,6 +213,7 @@ DEV void wgd_scan(WgDecState& S, const WgDecReq& q, const Tables& t) {
     if (!get_varint(pb, wire_len, &pos, &tag)) { ok = false; break; }
     uint32_t num = (uint32_t)(tag >> 3), wt = (uint32_t)(tag & 7);
     if ((tag >> 3) - 1 >= MAX_FIELD_NUMBER) { ok = false; break; }
+    const bool run_start = num != cur;
     if (num != cur) {
       // close the previous run: its last chunk keeps the bracket
       if (n > 0) S.tail[n - 1] = 0;
@@ -166,6 +228,7 @@ DEV void wgd_scan(WgDecState& S, const WgDecReq& q, const Tables& t) {
         const FieldEntry& fe = t.fields[tm.field_start + fi];
         if (fe.number != num) continue;
         cur_fe = &fe;
+        cur_fi = fi;
         bool per_entry_len =
             (fe.flags & F_MAP) ||
             ((fe.flags & F_REPEATED) &&
@@ -190,6 +253,7 @@ DEV void wgd_scan(WgDecState& S, const WgDecReq& q, const Tables& t) {
           if (n + 1 >= WG_DEC_MAX_ITEMS) { ok = false; break; }
           S.head[n] = 0;
           S.tail[n] = 0;
+          S.pchunk[n] = WGD_PK_NONE;
           S.outlen[n] = prev_num;
           S.src[n] = num;
           S.start[n++] = tag_start;
@@ -197,6 +261,7 @@ DEV void wgd_scan(WgDecState& S, const WgDecReq& q, const Tables& t) {
       }
       S.head[n] = 0;
       S.tail[n] = (uint8_t)(cur_split ? 1 : 0);
+      S.pchunk[n] = WGD_PK_NONE;
       S.start[n++] = tag_start;
       prev_num = num;
       cur = num;
@@ -206,6 +271,7 @@ DEV void wgd_scan(WgDecState& S, const WgDecReq& q, const Tables& t) {
       if (n >= WG_DEC_MAX_ITEMS) { ok = false; break; }
       S.head[n] = (uint16_t)chunk_head;
       S.tail[n] = 1;
+      S.pchunk[n] = WGD_PK_NONE;
       S.start[n++] = tag_start;
       chunk_wire = 0;
     }
@@ -232,6 +298,24 @@ DEV void wgd_scan(WgDecState& S, const WgDecReq& q, const Tables& t) {
       if (v > wire_len - pos) { ok = false; break; }
       // ... and an empty packed run is no occurrence of its field
       if (packed_run && v == 0) { ok = false; break; }
+      // a packed run that is this one record and nothing else, two chunks or
+      // more long: its body is cut into chunk items (wgd_pack_split)
+      if (run_start && cur_fe != nullptr && (cur_fe->flags & F_REPEATED) &&
+          expected_wire(*cur_fe) != W_LEN && cur_fi <= 0xFFFF &&
+          v >= 2u * WG_DEC_PACK_CHUNK) {
+        uint32_t np = pos + (uint32_t)v;
+        uint64_t nt = 0;
+        bool alone = np == wire_len ||
+                     (get_varint(pb, wire_len, &np, &nt) && (nt >> 3) != num);
+        if (alone) {
+          // every later field takes an item, and a fill item under
+          // DM_UNPOPULATED, as does the wire's end
+          int keep = tm.field_count - 1 - cur_fi;
+          if (unpop) keep = 2 * keep + 1;
+          n = wgd_pack_split(S, n, pb, pos, (uint32_t)v,
+                             expected_wire(*cur_fe) == W_VARINT, cur_fi, keep);
+        }
+      }
       pos += (uint32_t)v;
     } else {
       ok = false;
@@ -247,6 +331,7 @@ DEV void wgd_scan(WgDecState& S, const WgDecReq& q, const Tables& t) {
       } else {
         S.head[n] = 0;
         S.tail[n] = 0;
+        S.pchunk[n] = WGD_PK_NONE;
         S.outlen[n] = prev_num;
         S.src[n] = 0xFFFFFFFFu;
         S.start[n++] = wire_len;
@@ -292,6 +377,24 @@ DEV void wgd_fill(WgDecState& S, const WgDecReq& q, const Tables& t) {
   }
 }
 
+// ---- phase B, a packed chunk: its elements through emit_packed, no walk.
+// The first chunk steps over the tag and the length the scanner read and
+// opens the array as decode_walk does, the last one closes it; the comma
+// between two chunks is the joiner's.  Out of line: wgd_walk keeps the
+// registers it had
+DEVN bool wgd_pack_walk(DCtx& c, const FieldEntry& fe, uint32_t end, uint8_t pk) {
+  if (pk == WGD_PK_FIRST) {
+    uint64_t v;
+    if (!read_varint(c, &v) || !read_varint(c, &v) || !putc_(c, '"') ||
+        !puts_(c, (const char*)(c.t.names + fe.json_off), fe.json_len) ||
+        !puts_(c, "\":[", 3))
+      return false;
+  }
+  bool first = true;
+  if (!emit_packed(c, fe, end, &first)) return false;
+  return pk != WGD_PK_LAST || putc_(c, ']');
+}
+
 // ---- phase B, items: decode (dynamic wave grabs; the guard bound makes
 // the loop provably finite — a wave can win at most n_items grabs) ----------
 DEV void wgd_walk(WgDecState& S, const WgDecReq& q, const Tables& t) {
@@ -320,7 +423,14 @@ DEV void wgd_walk(WgDecState& S, const WgDecReq& q, const Tables& t) {
     c.len = ien;
     c.pos = ist;
     c.unpop = (uint32_t)(q.flags & DM_UNPOPULATED);
-    bool ok = decode_walk(c, q.msg_idx, ien, /*bare_top=*/true);
+    bool ok;
+    if (S.pchunk[idx] == WGD_PK_NONE) {
+      ok = decode_walk(c, q.msg_idx, ien, /*bare_top=*/true);
+    } else {
+      ok = wgd_pack_walk(
+          c, t.fields[t.msgs[q.msg_idx].field_start + S.pfield[idx]], ien,
+          S.pchunk[idx]);
+    }
     uint32_t trim = (uint32_t)S.head[idx] + S.tail[idx];
     if (!ok || c.status != E_OK || c.opos < trim) {
       if (!lane) {
@@ -574,6 +684,30 @@ DEV void wgd_req(WgDecReq& q, int req, const uint8_t* resp_bytes,
   q.idp = id_slots + (size_t)req * ID_SLOT_BYTES;
   q.flags = mode & (DM_UNPOPULATED | DM_STRUCTURED);
   q.max_phase = max_phase;
+}
+
+// wg_scan_probe's answer on both tiers (engine.cpp k_wg_scan_probe, one wave;
+// host_sim.cpp): out[0] = the item count, 0 for the classic pass, then
+// (start, end, kind) per item: kind 0 = a field run or an entry chunk of one,
+// 1 = a fill item, 2 = a packed chunk
+constexpr uint32_t WG_SCAN_PROBE_WORDS = 1 + 3 * (uint32_t)WG_DEC_MAX_ITEMS;
+DEV void wgd_scan_dump(const WgDecState& S, uint32_t* out) {
+  const int n = S.mode ? S.nitems : 0;
+  if (!lane_id()) out[0] = (uint32_t)n;
+  for (int i = lane_id(); i < n; i += WAVE) {
+    out[1 + 3 * i] = S.start[i];
+    out[2 + 3 * i] = S.start[i + 1];
+    out[3 + 3 * i] = S.pchunk[i] != WGD_PK_NONE ? 2u : wgd_is_fill(S, i) ? 1u : 0u;
+  }
+}
+
+// the dumped table as the probe's [(start, end, kind)]
+static inline std::vector<std::array<uint32_t, 3>> wgd_scan_items(
+    const uint32_t* out) {
+  std::vector<std::array<uint32_t, 3>> items(out[0]);
+  for (uint32_t i = 0; i < out[0]; ++i)
+    items[i] = {out[1 + 3 * i], out[2 + 3 * i], out[3 + 3 * i]};
+  return items;
 }
 
 #ifndef GGRMCP_HOST_SIM

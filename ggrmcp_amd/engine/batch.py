@@ -59,6 +59,7 @@ SR_SERVER_STREAMING = 2
 # which pass of k_json2pb_wg answered a routed slot (k_json2pb sets neither)
 SR_WG_ITEMS = 4
 SR_WG_CLASSIC = 8
+SR_WG_PACK = 16  # beside SR_WG_ITEMS: a packed array was split into chunks
 
 _STATUS_TO_RPC = {
     E_PARSE: (mcp.PARSE_ERROR, "parse error"),

@@ -64,6 +64,17 @@ class HostSimEngine:
         return [tuple(int(x) for x in it)
                 for it in self._eng.wg_scan_probe(bytes(wire), int(msg_idx), mode)]
 
+    def encode_packed_chunks(self, msg_idx: int, field_idx: int, text: bytes,
+                             cuts: Sequence[int]) -> Tuple[int, bytes]:
+        """``k_json2pb_wg``'s packed-array chunk items on the CPU build: the
+        element text of one array (no brackets) of the message's
+        ``field_idx``-th field, cut at the comma offsets ``cuts``; each chunk
+        through ``wg_pack_chunk``, the first as kind 4, joined by
+        ``wg_pack_backfill`` -> (status, wire; empty unless status is 0)."""
+        status, wire = self._eng.encode_packed_chunks(
+            int(msg_idx), int(field_idx), bytes(text), [int(c) for c in cuts])
+        return int(status), bytes(wire)
+
     def encode_batch(
         self,
         payloads: Sequence[bytes],

@@ -158,6 +158,8 @@ enum : uint32_t {
   // without a walk), or its in-block classic pass
   SR_WG_ITEMS = 4,
   SR_WG_CLASSIC = 8,
+  // beside SR_WG_ITEMS: a packed array was split into chunk items
+  SR_WG_PACK = 16,
 };
 
 // result of the decode (respond) kernel, one per request slot
@@ -494,6 +496,10 @@ constexpr uint32_t WG_ENC_MIN_BYTES = 16384;
 constexpr int WG_ENC_MAX_ITEMS = 384;
 constexpr uint32_t WG_ENC_ITEM_PAD = 160;
 constexpr int WG_ENC_WAVES = 16;
+// A top-level packed array is cut at the first element comma at or past every
+// WG_ENC_PACK_CHUNK bytes (item kinds 4 and 5), the stride of the map and
+// array chunkers; profiles/wg_packed_encode.md for the value.
+constexpr uint32_t WG_ENC_PACK_CHUNK = 4096;
 
 // Wire re-ordering (k_pb_reorder, DM_REORDER).  Each cap is a give-up rule:
 // the slot keeps E_UNSUPPORTED and the host answers it.

@@ -125,6 +125,28 @@ class HostEngine {
     return wgd_scan_items(out.data());
   }
 
+  // k_json2pb_wg's packed-array chunk items alone (json2pb.hip
+  // wg_pack_chunks_host): the element text of one array of the message's
+  // field_idx-th field, cut at the comma offsets `cuts` -> (status, wire)
+  py::tuple encode_packed_chunks(int msg_idx, int field_idx,
+                                 const std::string& text,
+                                 const std::vector<uint32_t>& cuts) {
+    if (msg_idx < 0 || msg_idx >= t_.n_msgs || field_idx < 0 ||
+        field_idx >= (int)t_.msgs[msg_idx].field_count)
+      throw std::invalid_argument("encode_packed_chunks: msg_idx / field_idx");
+    const int field = (int)t_.msgs[msg_idx].field_start + field_idx;
+    const FieldEntry& f = t_.fields[field];
+    if (!(f.flags & F_REPEATED) || (f.flags & F_MAP) || !is_packable(f.kind))
+      throw std::invalid_argument("encode_packed_chunks: not a packed array");
+    std::string wire;
+    int status = wg_pack_chunks_host(t_, field, (const uint8_t*)text.data(),
+                                     (uint32_t)text.size(), cuts.data(),
+                                     (int)cuts.size(), &wire);
+    if (status < 0)
+      throw std::invalid_argument("encode_packed_chunks: cuts");
+    return py::make_tuple(status, py::bytes(wire));
+  }
+
  private:
   py::tuple decode_impl(py::buffer data, py::array_t<uint32_t> resp_off,
                         py::array_t<uint32_t> scratch_off,
@@ -230,7 +252,22 @@ PYBIND11_MODULE(_hostsim, m) {
            py::arg("resp_off"), py::arg("scratch_off"), py::arg("final_off"),
            py::arg("msg_idx"), py::arg("skip"), py::arg("mode") = 0)
       .def("wg_scan_probe", &HostEngine::wg_scan_probe, py::arg("wire"),
-           py::arg("msg_idx"), py::arg("mode") = 0);
+           py::arg("msg_idx"), py::arg("mode") = 0)
+      .def("encode_packed_chunks", &HostEngine::encode_packed_chunks,
+           py::arg("msg_idx"), py::arg("field_idx"), py::arg("text"),
+           py::arg("cuts"));
+
+  // k_json2pb_wg phase C's length backfill (json2pb.hip wg_pack_backfill)
+  // for a split array of field `number` whose chunk items are `lens` bytes
+  // long: (fits, the 3 bytes of the length slot)
+  m.def("wg_pack_backfill", [](uint32_t number, std::vector<uint32_t> lens) {
+    uint8_t item[8] = {0};  // a tag is at most 5 bytes
+    bool ok = wg_pack_backfill(item, number, lens.data(), (int)lens.size());
+    uint32_t head = varint_len(((uint64_t)number << 3) | W_LEN);
+    return py::make_tuple(ok, py::bytes((const char*)item + head, LEN_SLOT));
+  }, py::arg("number"), py::arg("lens"));
+  m.attr("WG_ENC_PACK_CHUNK") = (int)WG_ENC_PACK_CHUNK;
+  m.attr("WG_ENC_ITEM_PAD") = (int)WG_ENC_ITEM_PAD;
 
   // k_pack_out's offset arithmetic (pb2json.hip pack_partial / pack_place,
   // summed over the kernel's 256 thread indices) for a batch of out_len

@@ -1625,18 +1625,29 @@ DEVN int encode_body_key(Ctx& c, EFrame& f) {
 // serial element below, which owns every error; after an empty window the
 // serial loop runs 1, 2, 4, .. 64 elements before the next attempt, so an
 // array the window cannot take costs little more than it did.
-DEVN bool encode_packed_array(Ctx& c, const FieldEntry& f) {
-  if (!emit_tag(c, f.number, W_LEN)) return false;
-  uint32_t slot;
-  if (!reserve_len(c, &slot)) return false;
+//
+// encode_packed_run is that loop, from an element start, with two ends.  The
+// whole array (`chunk` false) ends past its ']'.  A chunk of a split array
+// (k_json2pb_wg item kinds 4 and 5: c.len is the end of a span that holds
+// elements and the commas between them only) ends when an element and the
+// whitespace after it reach c.len.  The byte AT c.len is then the separator
+// that bounds the chunk, a cut comma or the array's ']', and the window (not
+// the serial element) may read it, so that it takes the chunk's last element
+// too: the serial element sends the doubles only the window converts to the
+// host.  A ']' inside a chunk, an empty chunk or one that ends in a comma is
+// an error here, whose code nobody reads: the caller hands the request to the
+// classic pass.
+DEVN bool encode_packed_run(Ctx& c, const FieldEntry& f, bool chunk) {
   const bool windowed = f.kind != K_BOOL && f.kind != K_ENUM;
   uint32_t serial_left = 0, backoff = 1;
   while (true) {
     if (windowed && serial_left == 0) {
-      PkWin w = pk_window(c.s, c.len, c.pos, c.out, c.opos, c.ocap, c.lane, f.kind);
+      PkWin w = pk_window(c.s, c.len + (chunk ? 1 : 0), c.pos, c.out, c.opos,
+                          c.ocap, c.lane, f.kind);
       c.pos = w.pos;
       c.opos = w.opos;
-      if (w.state == 2) break;
+      if (chunk && c.pos > c.len) return true;  // took the bounding separator
+      if (w.state == 2) return chunk ? fail(c, E_PARSE) : true;
       if (w.state == 1) {
         backoff = 1;
         continue;
@@ -1648,24 +1659,60 @@ DEVN bool encode_packed_array(Ctx& c, const FieldEntry& f) {
     skip_ws(c);
     if (!encode_packed_element(c, f)) return false;
     skip_ws(c);
+    if (chunk && c.pos == c.len) return true;
     uint8_t ch = peek(c);
     if (ch == ',') {
       c.pos++;
       continue;
     }
-    if (ch == ']') {
+    if (ch == ']' && !chunk) {
       c.pos++;
-      break;
+      return true;
     }
     return fail(c, E_PARSE);
   }
+}
+
+DEVN bool encode_packed_array(Ctx& c, const FieldEntry& f) {
+  if (!emit_tag(c, f.number, W_LEN)) return false;
+  uint32_t slot;
+  if (!reserve_len(c, &slot)) return false;
+  if (!encode_packed_run(c, f, false)) return false;
   return backfill_len(c, slot);
+}
+
+// One chunk item of a split packed array (k_json2pb_wg phase B).  The first
+// chunk (kind 4) opens the record: tag and an empty length slot, which
+// wg_pack_backfill fills once every chunk's length is known.
+DEV bool wg_pack_chunk(Ctx& c, const FieldEntry& f, bool first) {
+  if (first) {
+    uint32_t slot;
+    if (!emit_tag(c, f.number, W_LEN) || !reserve_len(c, &slot)) return false;
+  }
+  return encode_packed_run(c, f, true);
+}
+
+// Phase C: `olen` are the output lengths of a split array's n chunk items and
+// `item` is the first one's scratch.  Its length slot gets the payload bytes
+// of all of them; false when they exceed the slot (the classic pass then
+// reports the E_OVERFLOW).
+DEV bool wg_pack_backfill(uint8_t* item, uint32_t number, const uint32_t* olen,
+                          int n) {
+  const uint32_t head = varint_len(((uint64_t)number << 3) | W_LEN);
+  uint64_t total = 0;
+  for (int i = 0; i < n; ++i) total += olen[i];
+  if (total < head + LEN_SLOT || total - head - LEN_SLOT > LEN_SLOT_MAX)
+    return false;
+  put_varint_fixed(item + head, total - head - LEN_SLOT, LEN_SLOT);
+  return true;
 }
 
 // wg_item: workgroup-encode item modes (k_json2pb_wg). 0 = classic whole
 // value; 1 = one top-level member `"key": value`; 2 = map-entry span of
 // field wg_fidx (`"k":v, ...`, no braces); 3 = array-element span of
 // wg_fidx.  Item spans END the walk at c.len instead of a closing brace.
+// (Kinds 4 and 5, the chunks of a packed array, do not come here:
+// wg_pack_chunk.)
 DEV bool encode_walk(Ctx& c, int top_msg_idx, int wg_item = 0,
                      int wg_fidx = -1) {
   EFrame stack[MAX_RECURSE];
@@ -2300,11 +2347,16 @@ extern "C" __global__ void __launch_bounds__(WPB * WAVE) k_json2pb(
 //      top-level-member items; map members and non-packed repeated members
 //      chunk at entry/element boundaries (~4 KB) — protobuf wire
 //      CONCATENATION makes per-chunk emission valid with no joining
-//      fix-ups (repeated/map runs may split across tags).
+//      fix-ups (repeated/map runs may split across tags).  A packed
+//      repeated member chunks at element commas the same way (item kinds 4
+//      and 5): its chunks are ONE record, so only the first carries the tag
+//      and a length slot.
 //   B. waves grab items dynamically and encode each with the SAME
 //      encode_walk machinery (wg_item modes) into private scratch regions
-//      carved from the decode scratch arena (idle during encode).
-//   C. one thread prefix-sums item lengths; D. waves compact the items
+//      carved from the decode scratch arena (idle during encode); packed
+//      chunks go through wg_pack_chunk, no walk.
+//   C. one thread prefix-sums item lengths and writes each split array's
+//      summed length into its first chunk; D. waves compact the items
 //      into the slot's pb arena span.
 // Any anomaly (escaped member keys, duplicate fields, item errors, caps)
 // falls back to the classic single-wave encode inside the block, which
@@ -2487,11 +2539,14 @@ extern "C" __global__ void __launch_bounds__(WG_ENC_WAVES * WAVE) k_json2pb_wg(
             skip_ws(c);
             uint32_t member_start = kst - 1;  // include the opening quote
             bool chunk_map = (fe.flags & F_MAP) && peek(c) == '{';
-            bool chunk_arr = (fe.flags & F_REPEATED) &&
-                             !(fe.flags & F_MAP) && !is_packable(fe.kind) &&
-                             peek(c) == '[';
+            bool chunk_rep = (fe.flags & F_REPEATED) &&
+                             !(fe.flags & F_MAP) && peek(c) == '[';
+            bool chunk_arr = chunk_rep && !is_packable(fe.kind);
+            // a packed array: chunks of elements (kind 4, then 5), encoded
+            // by wg_pack_chunk and joined under one length in phase C
+            bool chunk_pack = chunk_rep && is_packable(fe.kind);
             bool big = (c.len - c.pos) >= 2048;
-            if ((chunk_map || chunk_arr) && big) {
+            if ((chunk_map || chunk_rep) && big) {
               // per-entry chunks: ONE bulk structural scan finds the
               // ~4 KB entry boundaries and the closer (the per-entry
               // string_span/skip_value loop paid a dependent memory
@@ -2506,7 +2561,8 @@ extern "C" __global__ void __launch_bounds__(WG_ENC_WAVES * WAVE) k_json2pb_wg(
                 uint32_t chunk_start = c.pos;
                 uint32_t marks[64];
                 int nm = 0;
-                if (!scan_container(c, marks, &nm, 64, 4096)) {
+                if (!scan_container(c, marks, &nm, 64,
+                                    chunk_pack ? WG_ENC_PACK_CHUNK : 4096)) {
                   fallback = true;
                   break;
                 }
@@ -2518,7 +2574,9 @@ extern "C" __global__ void __launch_bounds__(WG_ENC_WAVES * WAVE) k_json2pb_wg(
                 for (int mi2 = 0; mi2 <= nm && !fallback; ++mi2) {
                   uint32_t cs = mi2 == 0 ? chunk_start : marks[mi2 - 1] + 1;
                   uint32_t ce = mi2 == nm ? close_pos : marks[mi2];
-                  if (cs >= ce) continue;
+                  // an empty packed chunk ("1,,2", "[1,]" cut at that comma)
+                  // stays an item: it fails in phase B, classic answers
+                  if (cs >= ce && !chunk_pack) continue;
                   if (n >= WG_ENC_MAX_ITEMS) {
                     fallback = true;
                     break;
@@ -2533,7 +2591,7 @@ extern "C" __global__ void __launch_bounds__(WG_ENC_WAVES * WAVE) k_json2pb_wg(
                   s_end[n] = ce;
                   s_ioff[n] = acc;
                   s_fidx[n] = m.field_start + fidx;
-                  s_kind[n] = chunk_map ? 2 : 3;
+                  s_kind[n] = chunk_map ? 2 : chunk_arr ? 3 : mi2 ? 5 : 4;
                   ++n;
                   acc += icap;
                 }
@@ -2619,8 +2677,12 @@ extern "C" __global__ void __launch_bounds__(WG_ENC_WAVES * WAVE) k_json2pb_wg(
     __shared__ int16_t mwed[MW_WIN];
     __shared__ uint16_t mwc1[MW_WIN], mwc2[MW_WIN];
     __shared__ uint32_t mwp1[WG_ENC_MAX_ITEMS], mwp2[MW_D2];
+    // each window's first depth-2 comma: over MW_D2 commas they become mwp2
+    // (pass 2b), and chunks are cut at a window's first comma only
+    __shared__ uint32_t mwf2[MW_WIN];
+    static_assert(MW_WIN <= MW_D2, "the thinned comma list fits mwp2");
     __shared__ uint32_t s_ob, s_close, s_winb;
-    __shared__ int s_nwin, s_cwin, s_fb, s_n1, s_n2;
+    __shared__ int s_nwin, s_cwin, s_fb, s_n1, s_n2, s_thin;
     __shared__ unsigned long long s_seenf[2];
     __shared__ unsigned long long s_seeno;
     __shared__ uint16_t s_mcnt[WG_ENC_MAX_ITEMS];
@@ -2649,6 +2711,7 @@ extern "C" __global__ void __launch_bounds__(WG_ENC_WAVES * WAVE) k_json2pb_wg(
         s_close = 0;
         s_n1 = 0;
         s_n2 = 0;
+        s_thin = 0;
         s_seenf[0] = s_seenf[1] = 0;
         s_seeno = 0;
       }
@@ -2758,6 +2821,7 @@ extern "C" __global__ void __launch_bounds__(WG_ENC_WAVES * WAVE) k_json2pb_wg(
       const uint32_t base = s_ob + 1, wb = s_winb;
       for (int w = wave; w <= s_cwin; w += WG_ENC_WAVES) {
         int c1 = 0, c2 = 0;
+        uint32_t f2 = 0xFFFFFFFFu;  // none
         if ((int)mwed[w] + (int)mwdm[w][mwes[w]] <= 2) {
           uint32_t wst = base + (uint32_t)w * wb;
           uint32_t wen = wst + wb;
@@ -2806,10 +2870,12 @@ extern "C" __global__ void __launch_bounds__(WG_ENC_WAVES * WAVE) k_json2pb_wg(
                     }
                   }
                 } else if (ch == ',') {
-                  if (dep == 1)
+                  if (dep == 1) {
                     ++c1;
-                  else if (dep == 2)
+                  } else if (dep == 2) {
+                    if (!c2) f2 = pos;
                     ++c2;
+                  }
                 }
               }
             }
@@ -2818,6 +2884,7 @@ extern "C" __global__ void __launch_bounds__(WG_ENC_WAVES * WAVE) k_json2pb_wg(
         if (!lane) {
           mwc1[w] = (uint16_t)c1;
           mwc2[w] = (uint16_t)c2;
+          mwf2[w] = f2;
         }
       }
     }
@@ -2835,7 +2902,18 @@ extern "C" __global__ void __launch_bounds__(WG_ENC_WAVES * WAVE) k_json2pb_wg(
       }
       s_n1 = a1;
       s_n2 = a2;
-      if (a1 + 1 > WG_ENC_MAX_ITEMS || a2 > MW_D2) s_fb = 5;
+      if (a1 + 1 > WG_ENC_MAX_ITEMS) {
+        s_fb = 5;
+      } else if (a2 > MW_D2) {
+        // more depth-2 commas than mwp2 holds: keep each window's first one.
+        // Chunks then run to the first kept comma at or past the stride, a
+        // window longer at most; runs concatenate wherever they are cut.
+        int k = 0;
+        for (int w = 0; w <= s_cwin; ++w)
+          if (mwf2[w] != 0xFFFFFFFFu) mwp2[k++] = mwf2[w];
+        s_n2 = k;
+        s_thin = 1;
+      }
     }
     __syncthreads();
 
@@ -2851,6 +2929,7 @@ extern "C" __global__ void __launch_bounds__(WG_ENC_WAVES * WAVE) k_json2pb_wg(
         uint32_t sk = (stt == 2) ? wst : 0xFFFFFFFFu;
         if (stt == 2) stt = 1;
         int o1 = mwc1[w], o2 = mwc2[w];
+        const bool thin = s_thin != 0;  // mwp2 is final: depth-1 commas only
         for (uint32_t p = wst; p < wen && dep > 0; p += 4u * WAVE) {
           uint32_t off = p + 4u * (uint32_t)lane;
           uint32_t wd = load4_or(src, off, wen, 0);
@@ -2889,7 +2968,7 @@ extern "C" __global__ void __launch_bounds__(WG_ENC_WAVES * WAVE) k_json2pb_wg(
                 if (dep == 1) {
                   if (!lane) mwp1[o1] = pos;
                   ++o1;
-                } else if (dep == 2) {
+                } else if (dep == 2 && !thin) {
                   if (!lane) mwp2[o2] = pos;
                   ++o2;
                 }
@@ -2985,14 +3064,17 @@ extern "C" __global__ void __launch_bounds__(WG_ENC_WAVES * WAVE) k_json2pb_wg(
         while (vend > vstart && MW_IS_WS(src[vend - 1])) --vend;
         uint8_t vc = src[vstart];
         bool chunk_map = (fe.flags & F_MAP) && vc == '{';
-        bool chunk_arr = (fe.flags & F_REPEATED) && !(fe.flags & F_MAP) &&
-                         !is_packable(fe.kind) && vc == '[';
+        bool chunk_rep = (fe.flags & F_REPEATED) && !(fe.flags & F_MAP) &&
+                         vc == '[';
+        bool chunk_arr = chunk_rep && !is_packable(fe.kind);
+        bool chunk_pack = chunk_rep && is_packable(fe.kind);  // kinds 4, 5
         bool big = (s_args1 - vstart) >= 2048;
         int cnt = 0;
         uint32_t cap_sum = 0;
         uint32_t ibase = place ? s_mbase[m_i] : 0;
         uint32_t ioff = place ? s_moff[m_i] : 0;
-        if ((chunk_map || chunk_arr) && big) {
+        if ((chunk_map || chunk_rep) && big) {
+          const uint32_t stride = chunk_pack ? WG_ENC_PACK_CHUNK : 4096;
           uint8_t closer = chunk_map ? '}' : ']';
           if (vend <= vstart + 1 || src[vend - 1] != closer) {
             atomicExch(&s_fb, 6);
@@ -3012,13 +3094,14 @@ extern "C" __global__ void __launch_bounds__(WG_ENC_WAVES * WAVE) k_json2pb_wg(
               else
                 hi2 = mid;
             }
-            uint32_t prev_cs = cstart, nmark = cstart + 4096;
+            uint32_t prev_cs = cstart, nmark = cstart + stride;
             int nmk = 0;
             for (int q = lo2; q < s_n2 && nmk < 64; ++q) {
               uint32_t pos = mwp2[q];
               if (pos >= close_pos) break;
               if (pos >= nmark) {
-                if (prev_cs < pos) {
+                // an empty packed chunk stays an item (it fails in phase B)
+                if (prev_cs < pos || chunk_pack) {
                   uint32_t span = pos - prev_cs;
                   uint32_t icap = span + span / 4 + WG_ENC_ITEM_PAD;
                   if (place && !lane) {
@@ -3026,17 +3109,18 @@ extern "C" __global__ void __launch_bounds__(WG_ENC_WAVES * WAVE) k_json2pb_wg(
                     s_end[ibase + cnt] = pos;
                     s_ioff[ibase + cnt] = ioff + cap_sum;
                     s_fidx[ibase + cnt] = mm.field_start + fidx;
-                    s_kind[ibase + cnt] = chunk_map ? 2 : 3;
+                    s_kind[ibase + cnt] =
+                        chunk_map ? 2 : chunk_arr ? 3 : cnt ? 5 : 4;
                   }
                   ++cnt;
                   cap_sum += icap;
                 }
                 prev_cs = pos + 1;
-                nmark = pos + 4096;
+                nmark = pos + stride;
                 ++nmk;
               }
             }
-            if (prev_cs < close_pos) {
+            if (prev_cs < close_pos || chunk_pack) {
               uint32_t span = close_pos - prev_cs;
               uint32_t icap = span + span / 4 + WG_ENC_ITEM_PAD;
               if (place && !lane) {
@@ -3044,7 +3128,8 @@ extern "C" __global__ void __launch_bounds__(WG_ENC_WAVES * WAVE) k_json2pb_wg(
                 s_end[ibase + cnt] = close_pos;
                 s_ioff[ibase + cnt] = ioff + cap_sum;
                 s_fidx[ibase + cnt] = mm.field_start + fidx;
-                s_kind[ibase + cnt] = chunk_map ? 2 : 3;
+                s_kind[ibase + cnt] =
+                    chunk_map ? 2 : chunk_arr ? 3 : cnt ? 5 : 4;
               }
               ++cnt;
               cap_sum += icap;
@@ -3128,7 +3213,10 @@ extern "C" __global__ void __launch_bounds__(WG_ENC_WAVES * WAVE) k_json2pb_wg(
       c.aux = 0;
       c.lane = lane;
       c.keybuf = keybufs[wave];
-      bool ok = encode_walk(c, msg_idx, (int)s_kind[idx], s_fidx[idx]);
+      const int kind = (int)s_kind[idx];
+      bool ok = kind >= 4
+                    ? wg_pack_chunk(c, t.fields[s_fidx[idx]], kind == 4)
+                    : encode_walk(c, msg_idx, kind, s_fidx[idx]);
       if (!ok || c.status != E_OK) {
         // classic reproduces exact error position/detail formats
         if (!lane) atomicCAS(&s_mode, 1, 0);
@@ -3140,13 +3228,25 @@ extern "C" __global__ void __launch_bounds__(WG_ENC_WAVES * WAVE) k_json2pb_wg(
   __syncthreads();
 
   // ---- phase C: offsets (one thread) --------------------------------------
+  bool has_pack = false;  // thread 0: a split packed array was encoded
   if (s_mode == 1 && threadIdx.x == 0 && max_phase >= 2) {
     uint32_t off = 0;
+    bool fits = true;
     for (int i = 0; i < n_items; ++i) {
       s_foff[i] = off;
       off += s_olen[i];
+      if (s_kind[i] != 4) continue;
+      // a split packed array: one length over this chunk and its followers
+      // (the barrier below orders the store against phase D's copy)
+      int nc = 1;
+      while (i + nc < n_items && s_kind[i + nc] == 5 &&
+             s_fidx[i + nc] == s_fidx[i])
+        ++nc;
+      fits = fits && wg_pack_backfill(scr + s_ioff[i],
+                                      t.fields[s_fidx[i]].number, &s_olen[i], nc);
+      has_pack = true;
     }
-    if (off > pbcap) {
+    if (off > pbcap || !fits) {
       s_mode = 0;  // shouldn't happen (caps per item), but never truncate
     } else {
       s_res.pb_len = off;
@@ -3177,8 +3277,74 @@ extern "C" __global__ void __launch_bounds__(WG_ENC_WAVES * WAVE) k_json2pb_wg(
   // ---- finalize ------------------------------------------------------------
   if (s_mode != 0 && threadIdx.x == 0) {
     if (s_mode == 1 && max_phase < 2) s_res.pb_len = 0;  // debug phases
-    s_res.flags |= SR_WG_ITEMS;
+    s_res.flags |= SR_WG_ITEMS | (has_pack ? SR_WG_PACK : 0);
     results[req] = s_res;
   }
 }
+
+#else  // GGRMCP_HOST_SIM
+
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+// The packed-chunk pieces of k_json2pb_wg on the CPU build (the kernel itself
+// is not in it).  `text` is the element text of one array of field `field`
+// (absolute index), brackets left out, cut at the comma offsets `cuts`.  Each
+// chunk runs wg_pack_chunk at WAVE=1, the first as kind 4, from a heap copy of
+// exactly its bytes and its bounding separator into a heap item of exactly the
+// kernel's capacity;
+// wg_pack_backfill joins them and `wire` gets the record.  Returns the first
+// failing chunk's status, E_OVERFLOW where the helper refuses, -1 for cuts
+// that are not ascending comma offsets.
+inline int wg_pack_chunks_host(const Tables& t, int field, const uint8_t* text,
+                               uint32_t n, const uint32_t* cuts, int n_cuts,
+                               std::string* wire) {
+  for (int i = 0; i < n_cuts; ++i)
+    if (cuts[i] >= n || text[cuts[i]] != ',' || (i && cuts[i] <= cuts[i - 1]))
+      return -1;
+  const FieldEntry& f = t.fields[field];
+  std::vector<uint8_t*> items;
+  std::vector<uint32_t> olen;
+  int status = E_OK;
+  for (int i = 0; i <= n_cuts && status == E_OK; ++i) {
+    const uint32_t cs = i ? cuts[i - 1] + 1 : 0, ce = i < n_cuts ? cuts[i] : n;
+    const uint32_t span = ce - cs;
+    // the span and the separator that bounds it: the cut comma, or the ']'
+    // that follows the last chunk in a request
+    uint8_t* in = (uint8_t*)malloc(span + 1);
+    memcpy(in, text + cs, span);
+    in[span] = i < n_cuts ? ',' : ']';
+    Ctx c;
+    c.s = in;
+    c.len = span;
+    c.pos = 0;
+    c.ocap = span + span / 4 + WG_ENC_ITEM_PAD;
+    c.out = (uint8_t*)malloc(c.ocap);
+    c.opos = 0;
+    c.t = t;
+    c.lim = Limits{};
+    c.status = E_OK;
+    c.err_pos = 0;
+    c.aux = 0;
+    c.lane = 0;
+    c.keybuf = nullptr;
+    bool ok = wg_pack_chunk(c, f, i == 0);
+    if (!ok || c.status != E_OK) status = c.status != E_OK ? c.status : E_PARSE;
+    free(in);
+    items.push_back(c.out);
+    olen.push_back(c.opos);
+  }
+  if (status == E_OK &&
+      !wg_pack_backfill(items[0], f.number, olen.data(), (int)olen.size()))
+    status = E_OVERFLOW;
+  wire->clear();
+  for (size_t i = 0; i < items.size(); ++i) {
+    if (status == E_OK) wire->append((const char*)items[i], olen[i]);
+    free(items[i]);
+  }
+  return status;
+}
+
 #endif  // GGRMCP_HOST_SIM
